@@ -10,12 +10,22 @@ into image order -- strong scaling of one fixed frame (the reference's column sp
 src/raytrace_launcher.js:65-101, src/renderers.js:88).
 
     python bench.py [--gpus N --steps K --warmup W] [--config cornell_box_path|bunny|SDF_Menger|dragon|ASimpleScene]
+                    [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline figure needs: it loads the scene, runs W warmup steps and K timed
+steps on the two-stream schedule, writes the last timed frame if --dump-outputs is given, and prints the
+line (roofline, cpu_baseline, parity and the stage split are null).  --full adds the instrumented steps
+(dominant kernel, per-stage split), the roofline, the CPU baseline and the parity check described below.
+--dump-outputs DIR writes what the last timed step handed back as DIR/<name>.npy (float32): `image`, the
+[H, W, 4] RGBA8 frame, and on one GPU `colors`, the [H, W, 4] f32 colours handed to setColor.  A frame too
+large for the 64 MB budget is written as a fixed seeded sample of its rows.  The scene and seed are fixed,
+so two builds run with the same arguments can be compared output for output.
 
 --gpus N > 1 without a torch.distributed environment spawns N rank processes of this script (one per
 GPU, RANK/LOCAL_RANK/WORLD_SIZE set, rendezvous on 127.0.0.1) before anything touches a GPU; under
 torchrun the environment is used as given.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including:
+Prints ONE JSON line on rank 0 (contract in the task statement), including, with --full:
   roofline      -- for the DOMINANT kernel (largest share of render-kernel time), against the resource
                    that binds it: "valu" (scene cache-resident: cornell, bunny, Menger,
                    ASimpleScene) reports the kernel's f64 TFLOP/s (PMC-counted f64 flops per launch, from
@@ -306,6 +316,50 @@ def roofline(config, bound, dom, avg_ms, launches, counts, samples_per_frame, bu
     return r
 
 
+def bench_line(args, scene_name, W, H, spp, depth, world, cb, backend, elapsed, build_id, t_build, t_upload):
+    """The bench line of a plain run: the headline figure and what identifies the run.  The keys that only a
+    --full run measures are present and null; main() fills them in."""
+    size = f"{W}²" if W == H else f"{W}x{H}"
+    return {
+        "metric": METRIC.format(scene=scene_name, size=size),
+        "value": W * H * spp * args.steps / elapsed, "unit": "pixel-samples/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+        "data": "reference scene graph (exported from the live reference, not synthetic), keyed RNG seed 1",
+        "config": {"workload": f"{scene_name} {W}x{H} {spp}spp depth {depth} (Incremental)", "width": W,
+                   "height": H, "spp": spp, "max_depth": depth, "parallelism": f"tiles{world}",
+                   "col_block": cb, "headline": args.config == HEADLINE and args.spp == 0,
+                   "gather_backend": backend if world > 1 else None, "gather": args.gather},
+        "full": args.full, "dump_outputs": args.dump_outputs,
+        "roofline": None, "cpu_baseline": None, "parity": None,
+        "build_id": build_id, "knobs": knobs(),
+        "kernel_ms_per_step": None,
+        "scene_build_s": round(t_build, 3), "scene_upload_s": round(t_upload, 3),
+        "events_lost": None, "frame_attempts": None, "stages_ms_per_step": None, "stage_launches_per_step": None,
+        "counts_per_sample": None,
+    }
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes over all of --dump-outputs' arrays
+
+
+def dump_outputs(dirname, arrays):
+    """Write each array (None: not produced by this run) as <dirname>/<name>.npy in float32.  Arrays that
+    would not fit their equal share of DUMP_BUDGET are written as a sample of their rows (axis 0) drawn
+    with a fixed seed, in increasing order: the same rows on every run of the same arguments."""
+    import numpy as np
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        row_bytes = 4 * max(1, a[0].size)
+        if a.shape[0] * row_bytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], share // row_bytes, replace=False))
+            a = a[rows]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -327,7 +381,16 @@ def main():
                          "(jsrt_render_device_accum, tiles.AccumGather); the image is the same bit for bit")
     ap.add_argument("--ab", action="store_true", help="allow JSRT_* environment knobs / JSRT_LIB variants (A/B runs; "
                     "the line records them under `knobs`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the instrumented steps (dominant kernel, stage split), the roofline, the CPU baseline "
+                         "and the parity check against the oracle; a plain run only warms up, times and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.events and not args.full:
+        ap.error("--events brackets the dominant kernel, which only a --full run determines: pass --full")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if knobs() and not args.ab:
         print(f"bench: refusing to time with library knobs set {knobs()} (A/B only: pass --ab)", file=sys.stderr)
         sys.exit(2)
@@ -400,11 +463,17 @@ def main():
         fg.gather()
         return st
 
-    # warmup; the last warmup step is fully instrumented and names the dominant kernel
-    st_full = None
-    for w in range(max(args.warmup, 1)):
-        st_full = step(ONE if w == max(args.warmup, 1) - 1 else None)
-    dom = max(st_full["stage_ms"], key=lambda k: st_full["stage_ms"][k])
+    # warmup; with --full the last warmup step (there is at least one) is fully instrumented and names the
+    # dominant kernel; a plain run warms up on the timed steps' own schedule
+    dom = None
+    if args.full:
+        st_full = None
+        for w in range(max(args.warmup, 1)):
+            st_full = step(ONE if w == max(args.warmup, 1) - 1 else None)
+        dom = max(st_full["stage_ms"], key=lambda k: st_full["stage_ms"][k])
+    else:
+        for w in range(args.warmup):
+            step()
     # timed region: HIP events bracket only the dominant kernel's launches (its average launch
     # duration for the roofline); events on every launch would add launch gaps to the step.  The last
     # timed step also writes the f32 colours handed to setColor (k_final, 16 B per pixel): the parity
@@ -427,19 +496,24 @@ def main():
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     elapsed = float(tt.item())
-    if not args.events:  # the dominant kernel's launches, timed on the one-stream schedule
-        stats = [step((1 << STAGES.index(dom)) | ONE)]
-    dom_ms = sum(s["stage_ms"][dom] for s in stats) / len(stats)
-    dom_launches = stats[0]["stage_launches"][dom]
-    # per-stage split: one more step after the timed region with every launch bracketed
-    st_after = step(ONE)
-    stage_ms, stage_launches, kernel_ms = st_after["stage_ms"], st_after["stage_launches"], st_after["kernel_ms"]
-    torch.cuda.synchronize()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"image": timed_image, "colors": timed_cols})
+    if args.full:
+        if not args.events:  # the dominant kernel's launches, timed on the one-stream schedule
+            stats = [step((1 << STAGES.index(dom)) | ONE)]
+        dom_ms = sum(s["stage_ms"][dom] for s in stats) / len(stats)
+        dom_launches = stats[0]["stage_launches"][dom]
+        # per-stage split: one more step after the timed region with every launch bracketed
+        st_after = step(ONE)
+        stage_ms, stage_launches, kernel_ms = st_after["stage_ms"], st_after["stage_launches"], st_after["kernel_ms"]
+        torch.cuda.synchronize()
 
     par = None
-    if rank == 0:
-        total = W * H * spp
-        value = total * args.steps / elapsed
+    if rank == 0 and not args.full:
+        print(json.dumps(bench_line(args, scene_name, W, H, spp, depth, world, cb, backend, elapsed, jr._native.build_id(),
+                                    t_build, t_upload)))
+        sys.stdout.flush()
+    elif rank == 0:
         cpu, counts, ref = None, None, None
         if not args.no_cpu_baseline and world == 1:
             cpu, counts, ref = cpu_baseline(blob, W, H, spp, kind, depth)
@@ -461,21 +535,11 @@ def main():
             par["frame"] = "last timed step"
         roof = roofline(args.config, bound, dom, dom_ms / max(dom_launches, 1), dom_launches, counts, fg.ncols * H * spp,
                         jr._native.build_id())
-        size = f"{W}²" if W == H else f"{W}x{H}"
-        line = {
-            "metric": METRIC.format(scene=scene_name, size=size),
-            "value": value, "unit": "pixel-samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f64",
-            "data": "reference scene graph (exported from the live reference, not synthetic), keyed RNG seed 1",
-            "config": {"workload": f"{scene_name} {W}x{H} {spp}spp depth {depth} (Incremental)", "width": W,
-                       "height": H, "spp": spp, "max_depth": depth, "parallelism": f"tiles{world}",
-                       "col_block": cb, "headline": args.config == HEADLINE and args.spp == 0,
-                       "gather_backend": backend if world > 1 else None, "gather": args.gather},
+        line = bench_line(args, scene_name, W, H, spp, depth, world, cb, backend, elapsed, jr._native.build_id(),
+                          t_build, t_upload)
+        line.update({
             "roofline": roof, "cpu_baseline": cpu, "parity": par,
-            "build_id": jr._native.build_id(), "knobs": knobs(),
             "kernel_ms_per_step": kernel_ms,
-            "scene_build_s": round(t_build, 3), "scene_upload_s": round(t_upload, 3),
             "events_lost": {"timed": sum(x["events_lost"] for x in stats), "stage_split": st_after["events_lost"]},
             "frame_attempts": [x["attempts"] for x in stats],
             "stages_note": "stage split from one fully-instrumented step after the timed region, run on one "
@@ -483,7 +547,7 @@ def main():
             "stages_ms_per_step": {k: round(v, 3) for k, v in stage_ms.items() if v},
             "stage_launches_per_step": {k: v for k, v in stage_launches.items() if v},
             "counts_per_sample": {k: round(v, 4) for k, v in counts.items() if k != "samples"} if counts else None,
-        }
+        })
         print(json.dumps(line))
         sys.stdout.flush()
     if world > 1:

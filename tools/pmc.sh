@@ -1,8 +1,10 @@
 #!/bin/bash
 # GPU-box helper: PMC passes (one rocprofv3 --pmc pass per counter group, kernel-trace only) on a
-# one-step bench of CFG using library variant LIBV (JSRT_LIB), output under gpurun_out/pmc_<tag>/.
+# one-step bench of CFG using library variant LIBV (JSRT_LIB), output under $OUT/pmc_<tag>/ (OUT: BENCH_OUT, default bench_out).
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
+export OUT=${BENCH_OUT:-bench_out}  # where this script writes its logs and bench lines
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 CFG=${1:-cornell_box_path}; LIBV=${2:-}; TAG=${3:-$CFG}
 [ -n "$LIBV" ] && export JSRT_LIB=$PWD/jsraytracer_amd/_build/libjsrt_$LIBV.so
@@ -15,7 +17,7 @@ P6="SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MIS
 i=0
 for P in "$P1" "$P2" "$P3" "$P4" "$P5" "$P6"; do
   i=$((i+1))
-  mkdir -p gpurun_out/pmc_$TAG; timeout -k 10 600 rocprofv3 --pmc $P --kernel-trace --output-format csv -d gpurun_out/pmc_$TAG/p$i -o run -- \
-     python bench.py --config "$CFG" --steps 1 --warmup 0 --no-cpu-baseline --no-parity --ab ${PMC_BENCH_ARGS:-} > gpurun_out/pmc_$TAG/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 gpurun_out/pmc_$TAG/p$i.log; exit 1; }
+  mkdir -p $OUT/pmc_$TAG; timeout -k 10 600 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $OUT/pmc_$TAG/p$i -o run -- \
+     python bench.py --full --config "$CFG" --steps 1 --warmup 0 --no-cpu-baseline --no-parity --ab ${PMC_BENCH_ARGS:-} > $OUT/pmc_$TAG/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $OUT/pmc_$TAG/p$i.log; exit 1; }
 done
-python tools/pmc_summary.py gpurun_out/pmc_$TAG --config "$CFG" --merge gpurun_out/pmc_$TAG/pmc_merge.json > gpurun_out/pmc_$TAG/summary.txt && cat gpurun_out/pmc_$TAG/summary.txt
+python tools/pmc_summary.py $OUT/pmc_$TAG --config "$CFG" --merge $OUT/pmc_$TAG/pmc_merge.json > $OUT/pmc_$TAG/summary.txt && cat $OUT/pmc_$TAG/summary.txt
