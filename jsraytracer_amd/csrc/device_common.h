@@ -1071,13 +1071,15 @@ JSRT_HD float xf_row_dir(const T *r, F3 d) {
 // `inv` (rows 0..2), for a caller that accepts minD < t < lim: a planar primitive whose plane
 // distance already fails that test may return it without transforming the x/y rows or testing its
 // bounds; the caller's decision is unchanged.
+// lo (optional): the local origin xf_point(inv, o), where the caller already holds it (the node-per-lane shadow
+// cast transforms a node's origin once for all its samples); its rows are xf_row_point's own operations
 template <class T>
-JSRT_HD double planar_intersect(int k, const T *inv, F3 o, F3 d, double minD, double lim) {
+JSRT_HD double planar_intersect(int k, const T *inv, F3 o, F3 d, double minD, double lim, const F3 *lo = nullptr) {
     // SimplePlane.intersect (geometry.js:246-248) needs only the local z row
-    const float oz = xf_row_point(inv + 8, o), dz = xf_row_dir(inv + 8, d);
+    const float oz = lo ? lo->z : xf_row_point(inv + 8, o), dz = xf_row_dir(inv + 8, d);
     const double t = (dz != 0.0f) ? -(double)oz / (double)dz : -(double)__builtin_inf();
     if (k == JSRT_GEOM_PLANE || !(t > minD && t < lim)) return t;
-    const float ox = xf_row_point(inv, o), oy = xf_row_point(inv + 4, o);
+    const float ox = lo ? lo->x : xf_row_point(inv, o), oy = lo ? lo->y : xf_row_point(inv + 4, o);
     const float dx = xf_row_dir(inv, d), dy = xf_row_dir(inv + 4, d);
     const F3 p = ray_point(f3(ox, oy, oz), f3(dx, dy, dz), t);
     if (k == JSRT_GEOM_SQUARE)  // geometry.js:287-291
@@ -1110,9 +1112,10 @@ __device__ __forceinline__ float xf_row_dir_x(const T *r, F3 d) {
 // path forms from the f64 distance with two f32 roundings, moves by at most 2^-18 (|d t| + |o|) per
 // component under the estimate, so a bound test decided outside that margin is the exact test's outcome.
 template <class T>
-JSRT_HD int planar_any_f32(int k, const T *inv, F3 o, F3 d, double minD, double maxD, double &t_out) {
+JSRT_HD int planar_any_f32(int k, const T *inv, F3 o, F3 d, double minD, double maxD, double &t_out,
+                           const F3 *lo = nullptr) {  // lo: as planar_intersect's
     constexpr float EPS = 4.76837158203125e-7f, EPSP = 3.814697265625e-6f, TINY = 1e-30f;  // 2^-21, 2^-18
-    const float oz = XROWP(inv + 8, o), dz = XROWD(inv + 8, d);
+    const float oz = lo ? lo->z : XROWP(inv + 8, o), dz = XROWD(inv + 8, d);
     if (dz == 0.0f) return 0;  // t = -inf (planar_intersect's dz == 0 case): never accepted
 #ifdef __HIP_DEVICE_COMPILE__
     const float ta = -oz * __builtin_amdgcn_rcpf(dz);  // v_rcp_f32: within 1 ulp
@@ -1129,7 +1132,7 @@ JSRT_HD int planar_any_f32(int k, const T *inv, F3 o, F3 d, double minD, double 
         t_out = ta;
         return 1;
     }
-    const float ox = XROWP(inv, o), oy = XROWP(inv + 4, o);
+    const float ox = lo ? lo->x : XROWP(inv, o), oy = lo ? lo->y : XROWP(inv + 4, o);
     const float dx = XROWD(inv, d), dy = XROWD(inv + 4, d);
     const double td = (double)ta;
     const float sx = (float)((double)dx * td), sy = (float)((double)dy * td);
@@ -1274,6 +1277,51 @@ __device__ __forceinline__ double prim_any(const DScene &S, const PT &P, F3 o, F
     return prim_intersect<PF>(S, P, o, d, minD, maxD, transp, maxD);
 }
 
+// prim_any with the origin's share of the work taken out (the node-per-lane shadow cast, world_any_node: the
+// samples of one lit node share their origin).  The reference stores inv_transform.times(origin) as an f32
+// vector per (ray, primitive); all rays of a node have the same one, so prim_local_origin computes it once and
+// prim_any_at tests one direction against it.  Every operation and rounding is prim_any's own: xf_point's
+// rows are xf_row_point's, and the filters and exact tests below are called exactly as prim_any calls them.
+template <class PT>
+JSRT_HD F3 prim_local_origin(const PT &P, F3 o) { return xf_point(P.inv, o); }
+
+// The geometry kinds whose test starts from the local origin: true with the distance as prim_any reads it.
+template <class PT>
+JSRT_HD bool prim_any_local(const PT &P, F3 o, F3 lo, F3 d, double minD, double maxD, double &out) {
+    const int k = P.gkind;
+    double t = 0;
+    out = 0;
+    if (k == JSRT_GEOM_AABB) {
+        const F3 ld = xf_dir(P.inv, d);
+        const int dec = box_any_f32(P.center, P.half, lo, box_ray(ld), minD, maxD, t);
+        out = dec >= 0 ? (dec ? t : -DINF) : aabb_intersect(P.center, P.half, lo, ld, minD, maxD);
+        return true;
+    }
+    if (k == JSRT_GEOM_PLANE || k == JSRT_GEOM_SQUARE || k == JSRT_GEOM_CIRCLE) {
+        const int dec = planar_any_f32(k, P.inv, o, d, minD, maxD, t, &lo);
+        out = dec >= 0 ? (dec ? t : -DINF) : planar_intersect(k, P.inv, o, d, minD, maxD, &lo);
+        return true;
+    }
+    if (k == JSRT_GEOM_SPHERE) {
+        const F3 ld = xf_dir(P.inv, d);
+        const int dec = sphere_any_f32(lo, ld, minD, maxD, t);
+        out = dec >= 0 ? (dec ? t : -DINF) : sphere_static(lo, ld, minD);
+        return true;
+    }
+    return false;
+}
+
+template <int PF, class PT>
+__device__ __forceinline__ double prim_any_at(const DScene &S, const PT &P, F3 o, F3 lo, F3 d, double minD,
+                                              double maxD, bool transp) {
+#ifndef JSRT_NO_ANY_FILTER
+    if (!transp && !P.casts_shadow) return DINF;
+    double t;
+    if (prim_any_local(P, o, lo, d, minD, maxD, t)) return t;
+#endif
+    return prim_any<PF>(S, P, o, d, minD, maxD, transp);
+}
+
 // Primitive.intersect for a closest-hit cast (world.js:7-15): the caller keeps a distance only when
 // minD < t < lim (lim = min(maxD, the closest hit so far)), so for an AABB or Sphere geometry the f32 filters
 // above decide that first; an accepted distance comes back exact (one division, box_closest_f32 /
@@ -1411,7 +1459,7 @@ __device__ __forceinline__ void nested_cast(const DScene &S, int inst, F3 o, F3 
 // cannot produce an accepted hit on the segment (minD, flim): the ray misses its world box inflated
 // by k|o| + e0 (flim = (float) of the far limit min(best, maxD)).
 template <class RBT>  // RootBound in any address space
-__device__ __forceinline__ bool root_needed(const RBT &RB, F3 o, float ix, float iy, float iz, float oabs,
+JSRT_HD bool root_needed(const RBT &RB, F3 o, float ix, float iy, float iz, float oabs,
                                             float fminD, float flim) {
     if (!RB.bounded) return true;
     const float e = RB.k * oabs + RB.e0;
@@ -1485,6 +1533,86 @@ __device__ __forceinline__ Hit world_cast(const DScene &S, F3 o, F3 d, double mi
         }
     }
     return best;
+}
+
+// root_needed in two steps: the slab bounds relative to the origin (per origin), then the ray's test (per
+// direction).  The same operations in the same order as root_needed.
+struct RootSlab {
+    float lx, hx, ly, hy, lz, hz;
+};
+template <class RBT>
+JSRT_HD RootSlab root_slab(const RBT &RB, F3 o, float oabs) {
+    const float e = RB.k * oabs + RB.e0;
+    return RootSlab{RB.lo[0] - e - o.x, RB.hi[0] + e - o.x, RB.lo[1] - e - o.y,
+                    RB.hi[1] + e - o.y, RB.lo[2] - e - o.z, RB.hi[2] + e - o.z};
+}
+JSRT_HD bool root_needed_at(const RootSlab &B, float ix, float iy, float iz, float fminD, float flim) {
+    float a0 = B.lx * ix, a1 = B.hx * ix;
+    float tn = fminf(a0, a1), tf = fmaxf(a0, a1);
+    a0 = B.ly * iy;
+    a1 = B.hy * iy;
+    tn = fmaxf(tn, fminf(a0, a1));
+    tf = fminf(tf, fmaxf(a0, a1));
+    a0 = B.lz * iz;
+    a1 = B.hz * iz;
+    tn = fmaxf(tn, fminf(a0, a1));
+    tf = fminf(tf, fmaxf(a0, a1));
+    return (tn <= tf) && (tf >= fminD) && (tn <= flim);
+}
+
+// The shadow casts of one lit node's light samples on ONE lane (k_shadow_node): NS shadow rays that share
+// their origin o, directions d[s]; bit s of `live` = sample s still wants its answer.  Returns the bits of the
+// samples no root shadows.  Each sample's answer is world_cast<PF, true>(S, o, d[s], minD, maxD, false, mask)'s
+// (an any-hit answer does not depend on the order of the tests): the same culls and the same any-hit tests with
+// the same roundings, but what depends only on (origin, root) -- the cull's slab bounds and the f32 local origin
+// the reference stores as inv_transform.times(origin) -- is computed once per root for the node's samples, and a
+// root's record is loaded once for all of them.  Flat scenes only (every root a Primitive or skipped, as
+// world_cast does in a profile without BVH / aggregate roots).
+template <int PF, int NS>
+__device__ __forceinline__ uint32_t world_any_node(const DScene &S, F3 o, const F3 (&d)[NS], uint32_t live, double minD,
+                                                   double maxD, uint64_t mask) {
+    static_assert(!(PF & (PF_BVH | PF_AGG)), "flat scenes only");
+    float ix[NS], iy[NS], iz[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        ix[s] = __builtin_amdgcn_rcpf(d[s].x);
+        iy[s] = __builtin_amdgcn_rcpf(d[s].y);
+        iz[s] = __builtin_amdgcn_rcpf(d[s].z);
+    }
+    const float oabs = fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z)));
+    const float fminD = (float)minD, flim = (float)maxD;  // (a live sample has no hit yet: its far limit is maxD)
+    for (int i = 0; i < S.n_roots; ++i) {
+        if (i < 64 && !((mask >> i) & 1ull)) continue;
+        if (!__any(live != 0u)) break;
+        const auto &R = as_const(S.rootrec)[i];  // wave-uniform: scalar loads, once for the node's samples
+        uint32_t need = live;
+        if (R.rb.bounded) {
+            const RootSlab B = root_slab(R.rb, o, oabs);
+            need = 0u;
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                if (((live >> s) & 1u) && root_needed_at(B, ix[s], iy[s], iz[s], fminD, flim)) need |= 1u << s;
+        }
+        if (!__any(need != 0u)) continue;
+        if (R.kind != INST_PRIM || !R.p.casts_shadow) continue;  // (uniform) Primitive.intersect: Infinity
+        if (need) {  // (a divergent if: the loop itself stays uniform)
+            const F3 lo = prim_local_origin(R.p, o);
+#pragma nounroll
+            for (int s = 0; s < NS; ++s) {  // one copy of the tests; s is uniform, the selects are scalar-conditioned
+                const bool mine = (need >> s) & 1u;
+                if (!__any(mine)) continue;
+                F3 ds = d[0];
+#pragma unroll
+                for (int k = 1; k < NS; ++k)
+                    if (s == k) ds = d[k];
+                if (mine) {
+                    const double t = prim_any_at<PF>(S, R.p, o, lo, ds, minD, maxD, false);
+                    if (t > minD && t < maxD) live &= ~(1u << s);
+                }
+            }
+        }
+    }
+    return live;
 }
 
 // The flat shadow loop (DScene::sroot): World.cast(P, delta, 1e-4, 1, false) as materials.js:250-252 reads it --

@@ -732,6 +732,10 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
         WArgs W = wf.args;
         W.ns = ns;
         W.group = group;
+        // the node-per-lane k_shadow_node where run_batch's conditions hold (one area light of 2..4 samples in a
+        // flat scene); JSRT_SHADOW_NODE=0/1 forces the lane-per-sample k_shadow / asks for the node form
+        const char *sn = getenv("JSRT_SHADOW_NODE");
+        W.shadow_node = (sn ? sn[0] == '1' : true) ? 1 : 0;
         W.chain = chain ? 1 : 0;
         W.hybrid = hybrid ? 1 : 0;
         W.cap = (uint32_t)cap;

@@ -95,6 +95,7 @@ struct WArgs {
     uint32_t p0, npix, s0, npaths;
     int32_t ns;        // light samples per lit node
     int32_t group;     // lanes per node in k_shadow: a power of two >= ns (<= 64), or 1 (serial)
+    int32_t shadow_node; // k_shadow_node (one lane per lit node) where the scene and the batch allow it (run_batch)
     int32_t chain;     // schedule
     int32_t hybrid;    // chain schedule with side chains (level counts on the device)
     uint32_t cap;      // chain schedule: slots per level (node [L * cap + slot]); npaths without side chains

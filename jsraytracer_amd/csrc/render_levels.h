@@ -1228,9 +1228,20 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADOW_OCC_FLAT : JSR
         }
     }
     if (CHAIN && !W.bucket && in) q = chain_slot(W, L, q);  // hand-off in level order: the chain's slot
+    // Bucketed: every slot below the level's lit total was filled by k_shade with a lit node (DESIGN.md §4.2
+    // "lit = in"), so no lane waits for the node record before its sample: only the node's first lane loads it,
+    // early, for the ambient and the info word its store carries.  (q < count: a slot k_shade did not fill --
+    // never -- must not send that store out of the level: chain slots lie below cap, tree nodes below the level's
+    // count.)  Unbucketed: the hand-off has a slot per node of the level, lit or not, and INFO_LIT says which.
+    // Used where it was measured to win: the BVH profiles (bunny k_shadow 22.01 -> 21.31 ms).  The flat profile's
+    // lane-per-sample form lost with it (cornell 40.74 -> 41.88 ms, profiles/shadow_node_ab_cornell.txt) and keeps
+    // the gather; its scenes with one small area light run k_shadow_node, which has it built in.
+    const bool slots_lit = PF != PF_ANALYTIC && W.bucket;
+    if (slots_lit) in = in && q < (CHAIN ? W.cap : count);
     const uint32_t i = base + (in ? q : 0u);
-    const float4 nd = W.node[i];
-    const bool lit = in && (f2u(nd.w) & INFO_LIT);
+    float4 nd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!slots_lit || s == 0) nd = W.node[i];
+    const bool lit = in && (slots_lit || (f2u(nd.w) & INFO_LIT));
     F3 ret = f3(nd.x, nd.y, nd.z);  // ambient
     if (SERIAL) {  // one lane per node: every sample in order
         if (!lit) return;
@@ -1261,6 +1272,98 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADOW_OCC_FLAT : JSR
     }
     ret = light_sums(S, G, ret, c);
     if (lit && s == 0) W.node[i] = make_float4(ret.x, ret.y, ret.z, nd.w);
+}
+
+// k_shadow with one lane per lit node (JSRT_SHADOW_NODE, run_batch's shadow_node_ok): for a flat scene with
+// LDS-staged tables, a bucketed hand-off and ONE area light of 2..NS samples.  What depends only on the node is
+// done once instead of once per sample lane: the hand-off planes and the tag are loaded and decoded once, the
+// material -> colour chain is followed once, each shadow root's record is loaded and the origin's share of its
+// cull and of its local transform computed once for the node's samples (world_any_node), and the samples are
+// added in a register in the reference's order (the SERIAL branch's sum: no shuffles).  Every hand-off slot
+// below the level's lit total is a lit node (DESIGN.md §4.2 "lit = in"), so the node record is not read before
+// the casts: its load is issued early and consumed by the final store.  Results are k_shadow's bit for bit.
+#ifndef JSRT_SHADOW_NODE_OCC
+#define JSRT_SHADOW_NODE_OCC 5
+#endif
+template <int PF, bool CHAIN, int NS>
+__global__ __launch_bounds__(256, JSRT_SHADOW_NODE_OCC) void k_shadow_node(DScene S, WArgs W, int L) {
+    const LevelRange R = CHAIN ? chain_level(W, L) : level_range(W, L);
+    const uint32_t count = R.count, base = R.base;
+    const uint32_t ns = (uint32_t)W.ns;
+    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+    const bool in = e < as_const(W.bkt + (size_t)L * BKT_LEVEL)[3 * BKT_K];
+    const uint32_t h = in ? e : 0u;
+    const float4 *hp = W.hand + h;
+    const size_t hs = W.hstride;
+    const uint32_t q = W.hnode[h];
+    const float4 h0 = hp[0], h1 = hp[hs];  // (before the staging barrier)
+    const uint32_t tag = f2u(h1.w);
+    uint64_t mask = ~0ull;  // the wave's shadow-root mask, as k_shadow's: 64 nodes of (nearly always) one cell
+    if (W.bucket_grid && S.grid_masked) {
+        const uint32_t mi = tag & 0xFFu;
+        const uint64_t on = __ballot(in);
+        if (on) {
+            const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)mi, __builtin_ctzll(on));
+            if (!__ballot(in && mi != m0) && m0 <= (uint32_t)S.grid_cells) mask = as_const(S.grid_mask)[m0];
+        }
+    }
+    // (a slot k_shade did not fill -- never, DESIGN.md §4.2 -- must not send the store out of the level: chain
+    // slots lie below cap, tree nodes below the level's count)
+    const bool lit = in && q < (CHAIN ? W.cap : count);
+    const uint32_t i = base + (lit ? q : 0u);
+    const float4 nd = W.node[i];  // the ambient and the info word: consumed by the store at the end
+    extern __shared__ uint4 stab_lds[];
+    const uint4 *src = reinterpret_cast<const uint4 *>(S.stab);
+    for (int k = (int)threadIdx.x; k < S.stab_words_shadow; k += 256) stab_lds[k] = src[k];
+    __syncthreads();
+    if (!lit) return;
+    DScene SL = S;
+    stab_bind(SL, stab_lds, false);
+    // per node: the material data of sample_unshadowed, once
+    const F3 P = f3(h0.x, h0.y, h0.z);
+    const jsrt_rec_material &M = SL.mat[(tag & HAND_MAT) >> 8];
+    ShadeData sd;
+    sd.N = f3(h1.x, h1.y, h1.z);
+    sd.diff = (tag & HAND_DIFF) ? f3(hp[2 * hs].x, hp[2 * hs].y, hp[2 * hs].z) : mc_const3(SL, M.diffuse);
+    sd.spec = (tag & HAND_SPEC) ? f3(hp[4 * hs].x, hp[4 * hs].y, hp[4 * hs].z) : mc_const3(SL, M.specular);
+    sd.R = f3(0, 0, 0);
+    sd.refr = f3(0, 0, 0);
+    sd.kr = 1.0;
+    if (tag & HAND_R) {
+        const float4 h3 = hp[3 * hs];
+        sd.R = f3(h3.x, h3.y, h3.z);
+        if (tag & HAND_KR) {
+            const float4 h5 = hp[5 * hs];
+            sd.refr = f3(h5.x, h5.y, h5.z);
+            sd.kr = __hiloint2double((int)f2u(h3.w), (int)f2u(h5.w));
+        }
+    }
+    sd.smoothness = M.smoothness;
+    const int mkind = (int)M.kind;
+    // per sample: the light sample and its unshadowed colour (sample_unshadowed's per-sample part)
+    F3 d[NS], c[NS];
+    uint32_t live = 0u;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        d[s] = f3(1, 1, 1);
+        c[s] = f3(0, 0, 0);
+        if ((uint32_t)s < ns) {
+            RngH rng{f2u(h0.w), (uint32_t)SL.sample_call[s]};
+            F3 Ld, lcol;
+            light_sample<false>(SL, as_const(S.lights)[0], P, rng, d[s], Ld, lcol);
+            c[s] = light_sample_color(mkind, sd, Ld, lcol, !(tag & HAND_R));
+            // (sample_color's skip: a colour of +-0 in every component adds nothing, its cast is not run)
+            if (!(c[s].x == 0.0f && c[s].y == 0.0f && c[s].z == 0.0f)) live |= 1u << s;
+        }
+    }
+    live = world_any_node<PF, NS>(S, P, d, live, 0.0001, 1, mask);
+    // colorFromLights: the light's samples in order (a shadowed or skipped one adds +0), times 1 / samples
+    F3 light_color = f3(0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+        if ((uint32_t)s < ns) light_color = add(light_color, ((live >> s) & 1u) ? c[s] : f3(0, 0, 0));
+    const F3 ret = add(f3(nd.x, nd.y, nd.z), scale(light_color, as_const(S.lights)[0].inv_n));
+    W.node[i] = make_float4(ret.x, ret.y, ret.z, nd.w);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1489,7 +1592,16 @@ void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t
                 } else if (W.ns <= 1 || W.group > 1) {
                     const dim3 g(grid_ub(ub * (size_t)W.group));
                     const size_t sl = (size_t)S.stab_words_shadow * 16;  // the LDS-staged tables (flat scenes)
-                    if (PF == PF_ANALYTIC && sl && S.sphere_lights && S.n_sroot > 0)
+                    // one lane per lit node (k_shadow_node): a flat scene with staged tables and a bucketed hand-off,
+                    // one area light without a Sphere geometry, 2..4 samples; everything else keeps k_shadow
+                    bool node_form = false;
+                    if constexpr (PF == PF_ANALYTIC)
+                        node_form = W.shadow_node && W.bucket && sl && S.n_lights == 1 && !S.sphere_lights && S.n_sroot == 0 &&
+                                    W.ns > 1 && W.ns <= 4;
+                    if (node_form) {
+                        if constexpr (PF == PF_ANALYTIC)
+                            hipLaunchKernelGGL((k_shadow_node<PF, CHAIN, 4>), dim3(grid_ub(ub)), dim3(256), sl, st, S, W, L);
+                    } else if (PF == PF_ANALYTIC && sl && S.sphere_lights && S.n_sroot > 0)
                         hipLaunchKernelGGL((k_shadow<PF, CHAIN, false, true, PF == PF_ANALYTIC, PF == PF_ANALYTIC>), g, dim3(256), sl, st, S, W, L);
                     else if (PF == PF_ANALYTIC && sl && S.n_sroot > 0)
                         hipLaunchKernelGGL((k_shadow<PF, CHAIN, false, false, PF == PF_ANALYTIC, PF == PF_ANALYTIC>), g, dim3(256), sl, st, S, W, L);
