@@ -305,7 +305,68 @@ EventPairs::~EventPairs() {
     for (auto x : e) (void)hipEventDestroy(x);
 }
 
-hipError_t Wavefront::reserve(size_t rays, size_t nodes, size_t hands, size_t paths, int mode, size_t shadow) {
+#ifndef TILE_PATCHES_DEFAULT
+#define TILE_PATCHES_DEFAULT 8
+#endif
+#ifndef SPLIT_PIXELS_DEFAULT
+#define SPLIT_PIXELS_DEFAULT true  // bunny 656.6 -> 687.2 M/s (profiles/r06_s9_bunny.txt)
+#endif
+// The run-time knobs of the render path (environment variables JSRT_<NAME>; A/B and test knobs), read once per
+// frame by frame_knobs(), the only getenv of this file.  -1 = unset: the default is decided where the knob is used.
+struct FrameKnobs {
+    bool force_exact_pick = false;  // FORCE_EXACT_PICK=1 (tests): every diffuse pick through k_fix_dirs
+    int fix_cap = -1;               // FIX_CAP=n (tests): n k_fix_dirs records until a frame runs out; default by pool
+    int hybrid = -1;                // HYBRID=0/1: the tree / the hybrid chain for branching scenes; default by profile
+    int pixel_major = -1;           // PIXEL_MAJOR=0/1: a pixel's samples side by side; default: not the analytic profile
+    uint32_t batch_spp = 256;       // BATCH_SPP=n: samples of a pixel per pixel-major batch (>= 1)
+    int tile_patches = TILE_PATCHES_DEFAULT;  // TILE_PATCHES=n: pixel-major pixels in tiles of n x n patches (0: raster)
+    bool persist = true;            // PERSIST=0: no persistent casts for SDF scenes
+    bool split_frame = true;        // SPLIT_FRAME=0: a frame that fits one batch stays one batch
+    int split_min = 22;             // SPLIT_MIN=k: ... and is split from 2^k paths (1..40)
+    bool split_pixels = SPLIT_PIXELS_DEFAULT;  // SPLIT_PIXELS=0/1: a pixel-major frame splits its pixels, not its samples
+    size_t pool_factor = 0;         // POOL_FACTOR=n (tests): the first pool, >= 1; 0: default by schedule and batch
+    double bound_margin = 1.25;     // BOUND_MARGIN=x (tests): learned launch bounds x this ...
+    size_t bound_slack = 4096;      // ... + this many rays (0 when BOUND_MARGIN is set)
+    int dual = -1;                  // DUAL=0/1: two batch pools on two streams; default: two comparable batches
+    int split = -1;                 // SPLIT=0/1: k_shadow on a stream of its own; default: persistent casts, one pool
+    bool shadow_serial = false;     // SHADOW_SERIAL=1: a node's light samples on one lane (not with persistent casts)
+    bool shadow_node = true;        // SHADOW_NODE=0: never the node-per-lane k_shadow_node
+    bool bucket = true;             // BUCKET=0: no bucketed shadow hand-off
+    int child_sort = -1;            // CHILD_SORT=0/1: children grouped by direction octant; default: BVH profiles
+    int bucket_grid = -1;           // BUCKET_GRID=0/1: buckets keyed by grid cell; default: the analytic profile
+};
+static FrameKnobs frame_knobs() {
+    auto is1 = [](const char *n) { const char *v = getenv(n); return v ? (v[0] == '1' ? 1 : 0) : -1; };  // -1 unset
+    auto not0 = [](const char *n) { const char *v = getenv(n); return !(v && v[0] == '0'); };
+    FrameKnobs K;
+    const char *v;
+    K.force_exact_pick = is1("JSRT_FORCE_EXACT_PICK") == 1;
+    if ((v = getenv("JSRT_FIX_CAP"))) K.fix_cap = std::max(0, atoi(v));
+    if ((v = getenv("JSRT_HYBRID"))) K.hybrid = v[0] == '0' ? 0 : 1;
+    K.pixel_major = is1("JSRT_PIXEL_MAJOR");
+    if ((v = getenv("JSRT_BATCH_SPP"))) K.batch_spp = (uint32_t)std::max(1, atoi(v));
+    if ((v = getenv("JSRT_TILE_PATCHES"))) K.tile_patches = std::max(0, atoi(v));
+    K.persist = not0("JSRT_PERSIST");
+    K.split_frame = not0("JSRT_SPLIT_FRAME");
+    if ((v = getenv("JSRT_SPLIT_MIN"))) K.split_min = std::max(1, std::min(40, atoi(v)));
+    if ((v = getenv("JSRT_SPLIT_PIXELS"))) K.split_pixels = v[0] == '1';
+    if ((v = getenv("JSRT_POOL_FACTOR"))) K.pool_factor = (size_t)std::max(1, atoi(v));
+    if ((v = getenv("JSRT_BOUND_MARGIN"))) {
+        K.bound_margin = atof(v);
+        K.bound_slack = 0;
+    }
+    K.dual = is1("JSRT_DUAL");
+    K.split = is1("JSRT_SPLIT");
+    K.shadow_serial = is1("JSRT_SHADOW_SERIAL") == 1;
+    K.shadow_node = is1("JSRT_SHADOW_NODE") != 0;
+    K.bucket = not0("JSRT_BUCKET");
+    K.child_sort = is1("JSRT_CHILD_SORT");
+    K.bucket_grid = is1("JSRT_BUCKET_GRID");
+    return K;
+}
+
+hipError_t Wavefront::reserve(size_t rays, size_t nodes, size_t hands, size_t paths, int mode, size_t shadow,
+                              const FrameKnobs &K) {
     const bool tree = mode == SCHED_TREE, hybrid = mode == SCHED_HYBRID;
     size_t bytes = 0;
     bytes += 8 * need(rays, 4) + need(rays, 8) + 2 * need(rays, 4);  // o d addr key + t + prim ctx
@@ -319,11 +380,9 @@ hipError_t Wavefront::reserve(size_t rays, size_t nodes, size_t hands, size_t pa
     bytes += need(64, 4) + need(2 * shadow, 16) + need(shadow, 16);  // work counters + shadow rays
     // unstable spherePicks per level: ~1e-5 of the nodes (k_fix_dirs); every node under JSRT_FORCE_EXACT_PICK,
     // or after a frame that ran out of records (fix_all: the frame is redone with one record per ray slot)
-    const char *fx = getenv("JSRT_FORCE_EXACT_PICK");
-    const bool force_fix = fx && fx[0] == '1';
     // (JSRT_FIX_CAP=n, a test knob: n records until a frame runs out, to exercise the redo on either pool)
-    const char *fc = getenv("JSRT_FIX_CAP");
-    const size_t fixcap = fix_all ? rays + 4096 : fc ? (size_t)std::max(0, atoi(fc)) : force_fix ? rays + 4096 : rays / 8 + 4096;
+    const bool force_fix = K.force_exact_pick;
+    const size_t fixcap = fix_all ? rays + 4096 : K.fix_cap >= 0 ? (size_t)K.fix_cap : force_fix ? rays + 4096 : rays / 8 + 4096;
     bytes += need(3 * fixcap, 16) + need(64, 4);
     if (tree || hybrid)  // buckets
         bytes += need(MAX_TREE_DEPTH * BKT_LEVEL, 4) + need((hands / 256 + 1) * BKT_N, 4) + need(rays, 4);
@@ -396,10 +455,9 @@ Wavefront::~Wavefront() {
 // one).  A/B on MI355X (profiles/r04_s6_ab.txt): cornell hybrid 493.8 vs tree 466.3 Ms/s; bunny 518.4 vs
 // 555.7, dragon 785.4 vs 792.5, SDF_Menger 112.8 vs 116.1 -- the tree's octant-sorted appends keep BVH
 // casts coherent, and its compaction suits sky-heavy scenes.
-int schedule_of(const DScene &S) {
+static int schedule_of(const DScene &S, const FrameKnobs &K) {
     if (S.max_children <= 1) return SCHED_CHAIN;
-    const char *hy = getenv("JSRT_HYBRID");
-    if (hy) return hy[0] == '0' ? SCHED_TREE : SCHED_HYBRID;
+    if (K.hybrid >= 0) return K.hybrid ? SCHED_HYBRID : SCHED_TREE;
     return S.profile == PF_ANALYTIC ? SCHED_HYBRID : SCHED_TREE;
 }
 constexpr size_t HYBRID_POOL_FACTOR = 2;  // initial hybrid side-chain slots: paths x factor / 4
@@ -409,7 +467,7 @@ size_t wavefront_bytes_per_path(const DScene &S, int ns, int max_depth) {
     const bool persist = (S.profile & PF_SDF) && S.all_roots_prims;
     size_t group = 1;
     while ((int)group < ns && ns <= 64) group *= 2;
-    const int sched = schedule_of(S);
+    const int sched = schedule_of(S, frame_knobs());
     const size_t depth = (size_t)std::max(1, max_depth);
     if (sched == SCHED_CHAIN)  // chain: one ray and depth nodes per path
         return ray + depth * node + hand + (persist ? group * 48 : 0);
@@ -536,27 +594,16 @@ void run_batch_pf(const DScene &S, const RenderArgs &A, const WArgs &W, hipStrea
 }
 }  // namespace
 
-#ifndef TILE_PATCHES_DEFAULT
-#define TILE_PATCHES_DEFAULT 8
-#endif
-#ifndef SPLIT_PIXELS_DEFAULT
-#define SPLIT_PIXELS_DEFAULT true  // bunny 656.6 -> 687.2 M/s (profiles/r06_s9_bunny.txt)
-#endif
-hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront &wf, hipStream_t st, KernelTimes *kt,
-                        size_t max_paths, const std::function<bool(int, double, bool)> &progress,
-                        const std::function<bool()> &due) {
-    if (!A.accum) return hipErrorInvalidValue;
+// The shape of a frame's batches: [p0, p0 + npix) pixels x [s0, s0 + nsb) samples each (no HIP calls)
+struct BatchPlan {
+    uint32_t npix, nsb;
+    bool pixel_major;   // WArgs::pixel_major
+    int tile_p;         // RenderArgs::tile_p
+    bool persist;       // persistent casts (SDF scenes whose top level is primitives only)
+    bool split_pixels;  // a split frame halves its pixels, not its samples
+};
+static BatchPlan plan_batches(const DScene &S, const RenderArgs &A, int ns, size_t max_paths, const FrameKnobs &K) {
     const uint32_t npix_total = (uint32_t)A.patches * 64u;
-    if (npix_total == 0) {  // a rank that owns no column (a multi-GPU frame narrower than its column blocks):
-        // nothing to trace, but an Incremental frame's passes are still reported, so that the rank's callbacks
-        // keep step with its peers' (tiles.render_progressive runs one collective per reported pass)
-        if (progress && A.kind == JSRT_RENDERER_INCREMENTAL) {
-            const uint32_t step = A.samples_per_batch > 0 ? (uint32_t)A.samples_per_batch : (uint32_t)A.spp;
-            for (uint32_t s_end = step; s_end < (uint32_t)A.spp; s_end += step)
-                if ((!due || due()) && !progress((int)s_end - 1, (double)s_end / A.spp, true)) break;
-        }
-        return hipSuccess;
-    }
     if (ns > 4) max_paths = max_paths * 4 / (size_t)ns;  // the per-sample hand-off scales with ns
     if (max_paths < 64) max_paths = 64;
     uint32_t npix = npix_total, nsb = 1;  // batch: [p0, p0 + npix) pixels x [s0, s0 + nsb) samples
@@ -572,12 +619,9 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
     // pixel-major order alone, then 1,116 / 1,228 / 1,306 / 1,416 / 1,475 / 1,533 M/s at 8 / 16 / 32 / 64 / 128 /
     // 256 samples per batch; the flat hybrid chain loses (cornell k_accum's strided reads), so it keeps the
     // sample-major order.  JSRT_PIXEL_MAJOR=0/1: A/B.
-    const char *pm = getenv("JSRT_PIXEL_MAJOR");
-    const bool pixel_major = pm ? pm[0] == '1' : S.profile != PF_ANALYTIC;
+    const bool pixel_major = K.pixel_major >= 0 ? K.pixel_major == 1 : S.profile != PF_ANALYTIC;
     if (pixel_major) {
-        const char *bs = getenv("JSRT_BATCH_SPP");
-        uint32_t want = (uint32_t)(bs ? std::max(1, atoi(bs)) : 256);
-        want = std::min<uint32_t>(want, (uint32_t)A.spp);
+        uint32_t want = std::min<uint32_t>(K.batch_spp, (uint32_t)A.spp);
         if (A.samples_per_batch > 0) want = std::min<uint32_t>(want, (uint32_t)A.samples_per_batch);
         if (nsb < want) {  // fewer pixels, more of their samples
             npix = (uint32_t)std::min<size_t>(npix_total, std::max<size_t>(64, (max_paths / want) & ~(size_t)63));
@@ -585,31 +629,47 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
         }
     }
     // ... and their pixels in compact tiles of JSRT_TILE_PATCHES x JSRT_TILE_PATCHES 8 x 8 patches (pixel_of)
-    RenderArgs At = A;
-    {
-        const char *tp = getenv("JSRT_TILE_PATCHES");
-        At.tile_p = pixel_major ? (tp ? std::max(0, atoi(tp)) : TILE_PATCHES_DEFAULT) : 0;
-    }
+    const int tile_p = pixel_major ? K.tile_patches : 0;
     // persistent casts: SDF scenes whose top level is primitives only (JSRT_PERSIST=0 disables)
-    const char *pe = getenv("JSRT_PERSIST");
-    const bool persist = (S.profile & PF_SDF) && S.all_roots_prims && !(pe && pe[0] == '0');
+    const bool persist = (S.profile & PF_SDF) && S.all_roots_prims && K.persist;
     // A frame that fits one batch of 4 M paths or more (a rank's columns of a multi-GPU render) is cut into
     // two batches of half the samples, so that they run on the two batch streams (below).  Round 3 split only
     // from 32 M paths (cornell 1024^2 x 32 +3.6 %; halves of 16 M lost 5 %, profiles/r03_s18_ab.txt s28); with
     // the hybrid chain the halves win down to 4 M: cornell's 4-rank share (16.7 M paths) 32.0 -> 29.5 ms, its
     // 8-rank share (8.4 M) 17.0 -> 16.3 ms (tools/project_scaling.py, profiles/r05_s6_projection.txt).
     // JSRT_SPLIT_FRAME=0 keeps one batch; JSRT_SPLIT_MIN=k (A/B) splits from 2^k paths.
-    const char *sf = getenv("JSRT_SPLIT_FRAME"), *sm = getenv("JSRT_SPLIT_MIN");  // (A/B: log2 of the paths)
-    const int split_min = sm ? std::max(1, std::min(40, atoi(sm))) : 22;
     // (Pixel-major batches split their pixels instead -- two halves of the image, every sample each -- so that the
     // rays in flight keep coming from few pixels; JSRT_SPLIT_PIXELS=0/1: A/B.)
-    const char *spx = getenv("JSRT_SPLIT_PIXELS");
-    const bool split_pixels = pixel_major && (spx ? spx[0] == '1' : SPLIT_PIXELS_DEFAULT);
-    if (!persist && !(sf && sf[0] == '0') && npix == npix_total && nsb == (uint32_t)A.spp && A.spp >= 2 &&
-        (uint64_t)npix * (uint64_t)A.spp >= ((uint64_t)1 << split_min)) {
+    const bool split_pixels = pixel_major && K.split_pixels;
+    if (!persist && K.split_frame && npix == npix_total && nsb == (uint32_t)A.spp && A.spp >= 2 &&
+        (uint64_t)npix * (uint64_t)A.spp >= ((uint64_t)1 << K.split_min)) {
         if (split_pixels && npix_total >= 128) npix = ((npix_total / 2) + 63) & ~63u;  // whole patches: 64-pixel units
         else nsb = (uint32_t)((A.spp + 1) / 2);  // odd spp: halves of (spp + 1) / 2 and (spp - 1) / 2 samples
     }
+    return BatchPlan{npix, nsb, pixel_major, tile_p, persist, split_pixels};
+}
+
+hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront &wf, hipStream_t st, KernelTimes *kt,
+                        size_t max_paths, const std::function<bool(int, double, bool)> &progress,
+                        const std::function<bool()> &due) {
+    if (!A.accum) return hipErrorInvalidValue;
+    const uint32_t npix_total = (uint32_t)A.patches * 64u;
+    if (npix_total == 0) {  // a rank that owns no column (a multi-GPU frame narrower than its column blocks):
+        // nothing to trace, but an Incremental frame's passes are still reported, so that the rank's callbacks
+        // keep step with its peers' (tiles.render_progressive runs one collective per reported pass)
+        if (progress && A.kind == JSRT_RENDERER_INCREMENTAL) {
+            const uint32_t step = A.samples_per_batch > 0 ? (uint32_t)A.samples_per_batch : (uint32_t)A.spp;
+            for (uint32_t s_end = step; s_end < (uint32_t)A.spp; s_end += step)
+                if ((!due || due()) && !progress((int)s_end - 1, (double)s_end / A.spp, true)) break;
+        }
+        return hipSuccess;
+    }
+    const FrameKnobs K = frame_knobs();  // per frame: a process may change its environment between renders
+    const BatchPlan plan = plan_batches(S, A, ns, max_paths, K);
+    const uint32_t npix = plan.npix, nsb = plan.nsb;
+    const bool persist = plan.persist;
+    RenderArgs At = A;
+    At.tile_p = plan.tile_p;
     // Chain schedule when no node can have two children: depth x paths node records, nothing can
     // overflow, batches are enqueued back to back.  Tree schedule otherwise: a ray pool for all
     // levels of a batch (one level may hold half of it), compacted level by level.  Its launches
@@ -621,19 +681,17 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
     // slot], no parent / path planes, one bottom-up resolve -- plus a side chain per second child (a slot
     // appended after the paths, cap = paths + paths x pool_factor / 4).  Its level counts (the side chains
     // started so far) live on the device; launch bounds, overflow and redo work as for the tree.
-    const int sched = schedule_of(S);
+    const int sched = schedule_of(S, K);
     const bool hybrid = sched == SCHED_HYBRID, chain = sched != SCHED_TREE, learned = sched != SCHED_CHAIN;
     const int depth = std::max(1, A.max_depth);
     const size_t paths = (size_t)npix * nsb;
     // test knobs: a smaller first pool / tighter learned bounds exercise the frame redo paths
-    const char *pf_env = getenv("JSRT_POOL_FACTOR"), *bm_env = getenv("JSRT_BOUND_MARGIN");
-    const double margin = bm_env ? atof(bm_env) : 1.25;
-    const size_t slack = bm_env ? 0 : 4096;
+    const double margin = K.bound_margin;
+    const size_t slack = K.bound_slack;
     if (learned && (wf.pool_paths != paths || wf.pool_mode != sched)) {  // learned pool / bounds: per batch shape
         // (a batch of at most 1 M paths starts with 3 side-chain slots per path: a band of columns through a
         // glass sphere outgrows the default 0.5 -- a redo the memory of small batches need not risk)
-        wf.pool_factor = pf_env ? std::max(1, atoi(pf_env))
-                                : (hybrid ? (paths <= ((size_t)1 << 20) ? 8 : HYBRID_POOL_FACTOR) : 8);
+        wf.pool_factor = K.pool_factor ? K.pool_factor : (hybrid ? (paths <= ((size_t)1 << 20) ? 8 : HYBRID_POOL_FACTOR) : 8);
         wf.frac.clear();
         wf.pool_paths = paths;
         wf.pool_mode = sched;
@@ -652,12 +710,11 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
     // A render that asks for its launches' own times (JSRT_EVENTS_ONE_STREAM) runs on one stream: a
     // launch's event interval is only its own time when no other batch's kernels share the CUs.
     const bool timed_launches = kt && kt->one_stream;
-    const char *de = getenv("JSRT_DUAL");
     // two streams need two batches of comparable size: a frame of one full batch and a small remainder
     // (bunny: 32 M + 1.2 M paths) has nothing to overlap; a split frame of odd spp (nsb and nsb - 1 samples)
     // does
     const bool two_full = (uint64_t)npix_total * (uint64_t)A.spp >= 2 * (uint64_t)npix * nsb - (uint64_t)npix;
-    bool dual = !timed_launches && nbatches > 1 && (de ? de[0] == '1' : (!persist && two_full));
+    bool dual = !timed_launches && nbatches > 1 && (K.dual >= 0 ? K.dual == 1 : (!persist && two_full));
     hipEvent_t ev_start = nullptr, ev_end = nullptr, ev_acc[2] = {nullptr, nullptr};
     auto release_events = [&] {
         for (hipEvent_t x : {ev_start, ev_end, ev_acc[0], ev_acc[1]})
@@ -679,8 +736,7 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
     // level L's shadow samples overlap level L + 1's march.  SDF_Menger +6.5 %; elsewhere it loses
     // (bunny on one stream -5 %; beside two batch streams cornell +-0, dragon -1.3 %; profiles/
     // r03_s18_ab.txt s22, s26).  JSRT_SPLIT=0/1 forces it.
-    const char *se = getenv("JSRT_SPLIT");
-    const bool split = !timed_launches && ns > 0 && (se ? se[0] == '1' : (persist && !dual));
+    const bool split = !timed_launches && ns > 0 && (K.split >= 0 ? K.split == 1 : (persist && !dual));
     auto aux_of = [&](Wavefront &w) -> hipError_t {
         hipError_t r = hipSuccess;
         if (!w.aux) r = hipStreamCreateWithFlags(&w.aux, hipStreamNonBlocking);
@@ -705,16 +761,15 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
         int group = 1;
         // k_shadow: a node's light samples on `group` lanes (one each), or all on one lane (group 1: more than
         // 64 samples, or JSRT_SHADOW_SERIAL=1, an A/B knob)
-        const char *ss = getenv("JSRT_SHADOW_SERIAL");
-        if (ns > 1 && ns <= 64 && !(ss && ss[0] == '1' && !persist))
+        if (ns > 1 && ns <= 64 && !(K.shadow_serial && !persist))
             while (group < ns) group *= 2;
         // hand-off slots: one per node of a level; level 0 holds all `paths` camera rays, the
         // deeper levels at most level_cap (k_shade poisons the batch before writing past it)
         const size_t hands = chain ? cap : std::max(level_cap, paths);
         const size_t shadow = persist ? hands * (size_t)group : 0;
         auto reserve = [&](Wavefront &w) {
-            return chain ? w.reserve(cap, cap * (size_t)depth, cap, paths, sched, shadow)
-                         : w.reserve(pool, pool, hands, paths, SCHED_TREE, shadow);
+            return chain ? w.reserve(cap, cap * (size_t)depth, cap, paths, sched, shadow, K)
+                         : w.reserve(pool, pool, hands, paths, SCHED_TREE, shadow, K);
         };
         e = reserve(wf);
         if (e == hipSuccess && dual) {
@@ -729,45 +784,35 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
             }
         }
         if (e != hipSuccess) break;
-        WArgs W = wf.args;
-        W.ns = ns;
-        W.group = group;
-        // the node-per-lane k_shadow_node where run_batch's conditions hold (one area light of 2..4 samples in a
-        // flat scene); JSRT_SHADOW_NODE=0/1 forces the lane-per-sample k_shadow / asks for the node form
-        const char *sn = getenv("JSRT_SHADOW_NODE");
-        W.shadow_node = (sn ? sn[0] == '1' : true) ? 1 : 0;
-        W.chain = chain ? 1 : 0;
-        W.hybrid = hybrid ? 1 : 0;
-        W.cap = (uint32_t)cap;
-        // shadow hand-off bucketed by hit primitive (<= BKT_N buckets of consecutive primitives)
-        const char *be = getenv("JSRT_BUCKET");
-        int shift = 0;
-        while (S.n_prims > 0 && ((S.n_prims - 1) >> shift) >= BKT_N) ++shift;
-        W.bucket = (learned && !persist && S.n_prims > 0 && ns > 0 && ns <= 64 && !(be && be[0] == '0')) ? shift + 1 : 0;
-        W.pool = pool;
-        W.level_cap = level_cap;
-        // children grouped by direction octant where the next cast walks a BVH (A/B on MI355X,
-        // profiles/r03_s3_ab.txt: bunny +5.5 %; cornell -0.8 %, its keyed append costing k_shade 3 ms)
-        const char *cs = getenv("JSRT_CHILD_SORT");
-        W.child_sort = !chain && (cs ? (cs[0] == '1') : ((S.profile & PF_BVH) != 0));  // (tree appends only)
-        // hand-off buckets keyed by the hit point's grid cell, with per-cell shadow-root masks, for flat
-        // scenes (cornell +1.5 %, r03_s15); by hit primitive (runs of consecutive triangles) for meshes,
-        // where the BVH and not the root loop carries the shadow casts (bunny +-0.2 %, r03_s6)
-        const char *bg = getenv("JSRT_BUCKET_GRID");
-        const bool grid = bg ? bg[0] == '1' : S.profile == PF_ANALYTIC;
-        W.bucket_grid = (W.bucket && S.grid_cells > 0 && grid) ? 1 : 0;
-        W.pixel_major = pixel_major ? 1 : 0;  // the order of a batch's paths (above)
-        WArgs W2 = W;  // the twin pool: the same settings over its own buffers
-        if (dual) {
-            const WArgs &t = wf.twin->args;
-            W2.ox = t.ox; W2.oy = t.oy; W2.oz = t.oz; W2.dx = t.dx; W2.dy = t.dy; W2.dz = t.dz;
-            W2.addr = t.addr; W2.key = t.key; W2.path = t.path; W2.parent = t.parent; W2.t = t.t;
-            W2.prim = t.prim; W2.ctx = t.ctx; W2.node = t.node; W2.child = t.child; W2.slot = t.slot;
-            W2.hand = t.hand; W2.hnode = t.hnode; W2.root = t.root; W2.lvl = t.lvl; W2.qctr = t.qctr; W2.sray = t.sray;
-            W2.scol = t.scol; W2.bkt = t.bkt; W2.bbase = t.bbase; W2.brank = t.brank;
-            W2.list0 = t.list0; W2.list1 = t.list1; W2.endl = t.endl;
-            W2.fixrec = t.fixrec; W2.fixctr = t.fixctr; W2.fixcap = t.fixcap;
-        }
+        // the frame's settings over a pool's own buffers (every pointer and stride stays the pool's)
+        auto settings = [&](WArgs W) {
+            W.ns = ns;
+            W.group = group;
+            // the node-per-lane k_shadow_node where run_batch's conditions hold (one area light of 2..4 samples in a
+            // flat scene); JSRT_SHADOW_NODE=0/1 forces the lane-per-sample k_shadow / asks for the node form
+            W.shadow_node = K.shadow_node ? 1 : 0;
+            W.chain = chain ? 1 : 0;
+            W.hybrid = hybrid ? 1 : 0;
+            W.cap = (uint32_t)cap;
+            // shadow hand-off bucketed by hit primitive (<= BKT_N buckets of consecutive primitives)
+            int shift = 0;
+            while (S.n_prims > 0 && ((S.n_prims - 1) >> shift) >= BKT_N) ++shift;
+            W.bucket = (learned && !persist && S.n_prims > 0 && ns > 0 && ns <= 64 && K.bucket) ? shift + 1 : 0;
+            W.pool = pool;
+            W.level_cap = level_cap;
+            // children grouped by direction octant where the next cast walks a BVH (A/B on MI355X,
+            // profiles/r03_s3_ab.txt: bunny +5.5 %; cornell -0.8 %, its keyed append costing k_shade 3 ms)
+            W.child_sort = !chain && (K.child_sort >= 0 ? K.child_sort == 1 : ((S.profile & PF_BVH) != 0));  // (tree appends only)
+            // hand-off buckets keyed by the hit point's grid cell, with per-cell shadow-root masks, for flat
+            // scenes (cornell +1.5 %, r03_s15); by hit primitive (runs of consecutive triangles) for meshes,
+            // where the BVH and not the root loop carries the shadow casts (bunny +-0.2 %, r03_s6)
+            const bool grid = K.bucket_grid >= 0 ? K.bucket_grid == 1 : S.profile == PF_ANALYTIC;
+            W.bucket_grid = (W.bucket && S.grid_cells > 0 && grid) ? 1 : 0;
+            W.pixel_major = plan.pixel_major ? 1 : 0;  // the order of a batch's paths (plan_batches)
+            return W;
+        };
+        WArgs W = settings(wf.args);
+        WArgs W2 = dual ? settings(wf.twin->args) : W;  // the twin pool: the same settings over its own buffers
         if ((e = hipMemsetAsync(A.accum, 0, (size_t)A.ncols * A.H * 4 * sizeof(float), st)) != hipSuccess) break;
         if ((e = hipMemsetAsync(W.lvl + LVL_UNDER, 0, 2 * sizeof(uint32_t), st)) != hipSuccess) break;  // frame flags
         if ((e = hipMemsetAsync(W.fixctr, 0, sizeof(uint32_t), st)) != hipSuccess) break;

@@ -139,8 +139,8 @@ struct Wavefront {  // owns the batch buffers (cached per scene)
     WArgs args{};
     // rays: ray slots; nodes: node records; hands: hand-off records; paths: root colours
     // shadow: light-sample entries of the persistent shadow casts (0 if unused)
-    // mode: 0 chain, 1 tree, 2 hybrid chain
-    hipError_t reserve(size_t rays, size_t nodes, size_t hands, size_t paths, int mode, size_t shadow = 0);
+    // mode: 0 chain, 1 tree, 2 hybrid chain; K: the frame's knobs (render.hip)
+    hipError_t reserve(size_t rays, size_t nodes, size_t hands, size_t paths, int mode, size_t shadow, const struct FrameKnobs &K);
     void release();  // frees the buffers (the learned pool / bounds stay)
     ~Wavefront();
 };

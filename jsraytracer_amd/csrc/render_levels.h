@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "device_common.h"
@@ -56,30 +57,6 @@
 #endif
 
 namespace jsrt {
-
-#ifdef JSRT_X_STAMPS
-// (timing experiment only) per-phase shader-clock cycles of k_shade: every 16th block's waves add each phase's
-// cycles into their own slot (no atomics: same-address atomics from many waves would serialise and swamp the
-// kernel), g_xst[slot][k] and the count in [slot][8 + k]; jsrt_x_stamps (render_pf.hip) sums the slots
-constexpr int XST_SLOTS = 32768;
-static __device__ unsigned long long g_xst[XST_SLOTS][16];
-template <class T>
-__device__ __forceinline__ void xst(int k, uint64_t &t, const T &dep) {
-    asm volatile("" ::"v"(dep));  // the phase ends when `dep` is available
-    const uint64_t now = __builtin_amdgcn_s_memtime();
-    const uint32_t slot = (blockIdx.x >> 4) * 4 + (threadIdx.x >> 6);
-    if (__lane_id() == 0 && (blockIdx.x & 15) == 0 && slot < XST_SLOTS) {
-        g_xst[slot][k] += (unsigned long long)(now - t);
-        g_xst[slot][8 + k] += 1ull;
-    }
-    t = now;
-}
-#define XST_BEGIN uint64_t xst_t = __builtin_amdgcn_s_memtime();
-#define XST(k, dep) xst(k, xst_t, dep)
-#else
-#define XST_BEGIN
-#define XST(k, dep)
-#endif
 
 constexpr uint32_t NO_PARENT = 0xFFFFFFFFu;  // camera ray: its result is the path's root colour
 constexpr uint32_t DEAD_RAY = 0xFFFFFFFEu;   // level-0 slot of a path outside the image (no result)
@@ -856,6 +833,15 @@ __device__ __forceinline__ void stab_bind(DScene &SL, const uint4 *lds, bool sha
     SL.shadeI = reinterpret_cast<const double *>(sb + SL.stab_off[STAB_SHADEI]);
     SL.prim_lit = reinterpret_cast<const int32_t *>(sb + SL.stab_off[STAB_PRIM_LIT]);
 }
+// The first `words` 16-B words of DScene::stab copied into the block's dynamic LDS and bound in SL (the kernel's
+// own copy of S).  Every thread of the block must call it (a barrier).
+__device__ __forceinline__ void stab_stage(const DScene &S, DScene &SL, int words, bool shade) {
+    extern __shared__ uint4 stab_lds[];
+    const uint4 *src = reinterpret_cast<const uint4 *>(S.stab);
+    for (int k = (int)threadIdx.x; k < words; k += 256) stab_lds[k] = src[k];
+    __syncthreads();
+    stab_bind(SL, stab_lds, shade);
+}
 
 // STAGE (flat scenes whose shading tables fit, DScene::stab): the tables are copied into LDS by every block, so a
 // hit's dependent record chain (prim -> shading matrix / material -> colour constants) is LDS round trips
@@ -863,7 +849,6 @@ template <int PF, bool CHAIN, bool STAGE>
 __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
                                                     : (PF & PF_SDF) ? JSRT_SHADE_OCC_SDF : JSRT_SHADE_OCC) SHADE_ATTR void k_shade(
     DScene S, WArgs W, int L, int child_depth) {
-    XST_BEGIN
     const uint32_t t0 = blockIdx.x * 256, tt = t0 + threadIdx.x;
     const LevelRange R = CHAIN ? chain_level(W, L) : level_range(W, L);
     const uint32_t count = R.count, base = R.base, next_base = CHAIN ? 0u : R.base + R.count;
@@ -872,43 +857,8 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
     } else if (tt >= count) {
         return;
     }
-#ifdef JSRT_SHADE_SORT
-    // (A/B) the block's nodes permuted by hit primitive through LDS (a counting sort on min(prim, 62), misses
-    // and idle lanes last), so a wave shades nodes of one or two primitives: one geometry branch, one material
-    __shared__ uint32_t s_cnt[64], s_perm[256];
-    uint32_t tq = tt;
-    if (!CHAIN || W.hybrid) {  // (kernel argument: block-uniform; the plain chain returns per thread above)
-        uint32_t key = 63u;
-        if (tt < count) {
-            const uint32_t s0 = CHAIN ? chain_slot(W, L, tt) : tt;
-            const int p0 = W.prim[CHAIN ? s0 : base + tt];
-            key = p0 >= 0 ? (uint32_t)(p0 < 62 ? p0 : 62) : 63u;
-        }
-        if (threadIdx.x < 64) s_cnt[threadIdx.x] = 0u;
-        __syncthreads();
-        const uint32_t rank = atomicAdd(&s_cnt[key], 1u);
-        __syncthreads();
-        if (threadIdx.x < 64) {  // exclusive scan of the 64 counts in one wave
-            const uint32_t c = s_cnt[threadIdx.x];
-            uint32_t x = c;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t y = __shfl_up(x, o);
-                if ((int)threadIdx.x >= o) x += y;
-            }
-            s_cnt[threadIdx.x] = x - c;
-        }
-        __syncthreads();
-        s_perm[s_cnt[key] + rank] = threadIdx.x;
-        __syncthreads();
-        tq = t0 + s_perm[threadIdx.x];
-    }
-    const bool in = tq < count;
-    const uint32_t q = in ? tq : 0u;                          // level index
-#else
     const bool in = tt < count;
     const uint32_t q = in ? tt : 0u;                          // level index
-#endif
     const uint32_t slot = CHAIN && in ? chain_slot(W, L, q) : q;  // chain: the chain's slot
     const uint32_t i = base + (CHAIN ? slot : q);             // node index (chain: L * cap + slot)
     const uint32_t r = CHAIN ? slot : i;                      // ray index
@@ -933,14 +883,7 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
         rkey = W.key[r];
     }
     DScene SL = S;
-    if constexpr (STAGE) {
-        extern __shared__ uint4 stab_lds[];
-        const uint4 *src = reinterpret_cast<const uint4 *>(S.stab);
-        for (int k = (int)threadIdx.x; k < S.stab_words; k += 256) stab_lds[k] = src[k];
-        __syncthreads();
-        stab_bind(SL, stab_lds, true);
-    }
-    XST(0, prim);
+    if constexpr (STAGE) stab_stage(S, SL, S.stab_words, true);
     // Every load, and the children's append (a returning atomic), is issued before the node's first
     // store: vmcnt counts stores too, in issue order, so a load or atomic issued behind the node's
     // ~20 HBM stores would wait for all of them to complete.
@@ -971,7 +914,6 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
             if (W.bucket_grid) out.h.mask = (uint32_t)b;
         }
     }
-    XST(1, out.info);
     // tree: children append to level L + 1; at depth 0 they are black without a cast
     // W.child_sort: a block's children grouped by direction octant, so a wave of the next level's k_extend
     // casts rays of one or two octants that walk the same BVH subtrees (WArgs::child_sort)
@@ -993,7 +935,6 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
         block_append2(W.lvl + 2 * (L + 1), cont, side, at, side_at);
         side_at += side_base(W, L + 1);
     }
-    XST(2, side_at);
     // unstable spherePicks: the record for k_fix_dirs, with the slots the children's rays go to below (written
     // before the node's stores, behind which the returning atomic would wait for all of them)
     if (__builtin_expect(hit && (out.info & INFO_FIX) != 0u, 0) && child_depth > 0) {
@@ -1027,30 +968,21 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
     }
     if (nchild > 0 && unit_child(ch0)) out.info |= INFO_UNIT0;
     if (nchild > 1 && unit_child(ch1)) out.info |= INFO_UNIT1;
-    // (JSRT_X_*: timing-only experiments that drop one class of k_shade's stores; the image is wrong)
-#ifndef JSRT_X_NONODE
     store_node(W, i, out.surf, out.info & ~INFO_FIX);
-#endif
-#ifndef JSRT_X_NOHAND
     // (The record at the node's own index -- coalesced 16-B stores -- with k_shadow gathering it through hnode:
     // k_shade -1.5 ms, k_shadow +2.9 ms per cornell frame, profiles/r05_s5_s6_ab.txt; the scatter stays here.)
     if (out.info & INFO_LIT) {
         if (!W.bucket) store_hand(W, q, out.h);
         else if (hslot != ~0u) store_hand(W, hslot, out.h);
     }
-#endif
-#ifndef JSRT_X_NONODE
     if (nchild > 0) store_child(W, i, 0, ch0);
     if (nchild > 1) store_child(W, i, 1, ch1);
-#endif
     if (CHAIN) {  // the child ray (World.color(child, depth - 1)) takes over slot q
         uint32_t *next = (L & 1) ? W.list0 : W.list1;  // level L + 1's list
         if (child_depth > 0 && nchild > 0) {
-#ifndef JSRT_X_NORAY
             W.ox[r] = out.h.pos.x; W.oy[r] = out.h.pos.y; W.oz[r] = out.h.pos.z;
             W.dx[r] = ch0.dir.x; W.dy[r] = ch0.dir.y; W.dz[r] = ch0.dir.z;
             W.addr[r] = mix32(out.h.addr, 1u);
-#endif
             if (W.hybrid) next[at] = r;
         } else {
             W.prim[r] = NO_RAY;  // no child, or children black without a cast (depth 0)
@@ -1069,10 +1001,6 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
             W.parent[c] = i;
             W.prim[c] = -1;
         }
-#ifdef JSRT_X_STAMPS
-        __builtin_amdgcn_s_waitcnt(0);  // (the stores retired)
-        XST(3, r);
-#endif
         return;
     }
     if (nchild == 0) return;
@@ -1112,19 +1040,12 @@ __device__ __forceinline__ F3 mc_const3(const DScene &S, int m) {  // a constant
     const float4 c = *reinterpret_cast<const float4 *>(S.mc_const + 4 * m);
     return f3(c.x, c.y, c.z);
 }
-template <int PF, bool SPH = true>
-__device__ __forceinline__ F3 sample_unshadowed(const DScene &S, const float4 &h0, const float4 &h1, const float4 *hp,
-                                                size_t hs, uint32_t s, F3 &P, F3 &delta) {
-    P = f3(h0.x, h0.y, h0.z);
-    RngH rng{f2u(h0.w), (uint32_t)S.sample_call[s]};
-    F3 L, lcol;
-    if (S.n_lights == 1)  // (kernel argument: uniform) the light record through scalar loads
-        light_sample<SPH>(S, as_const(S.lights)[0], P, rng, delta, L, lcol);
-    else
-        light_sample<SPH>(S, S.lights[S.sample_light[s]], P, rng, delta, L, lcol);
+// A lit node's hand-off planes (store_hand; h1 = plane 1, already loaded) decoded into the material data of
+// colorFromLightSample: sd, the material's kind, and (returned) whether the specular term goes without R
+__device__ __forceinline__ bool hand_decode(const DScene &S, const float4 &h1, const float4 *hp, size_t hs, ShadeData &sd,
+                                            int &mkind) {
     const uint32_t tag = f2u(h1.w);
     const jsrt_rec_material &M = S.mat[(tag & HAND_MAT) >> 8];
-    ShadeData sd;
     sd.N = f3(h1.x, h1.y, h1.z);
     sd.diff = (tag & HAND_DIFF) ? f3(hp[2 * hs].x, hp[2 * hs].y, hp[2 * hs].z) : mc_const3(S, M.diffuse);
     sd.spec = (tag & HAND_SPEC) ? f3(hp[4 * hs].x, hp[4 * hs].y, hp[4 * hs].z) : mc_const3(S, M.specular);
@@ -1141,7 +1062,23 @@ __device__ __forceinline__ F3 sample_unshadowed(const DScene &S, const float4 &h
         }
     }
     sd.smoothness = M.smoothness;
-    return light_sample_color((int)M.kind, sd, L, lcol, !(tag & HAND_R));
+    mkind = (int)M.kind;
+    return !(tag & HAND_R);
+}
+template <int PF, bool SPH = true>
+__device__ __forceinline__ F3 sample_unshadowed(const DScene &S, const float4 &h0, const float4 &h1, const float4 *hp,
+                                                size_t hs, uint32_t s, F3 &P, F3 &delta) {
+    P = f3(h0.x, h0.y, h0.z);
+    RngH rng{f2u(h0.w), (uint32_t)S.sample_call[s]};
+    F3 L, lcol;
+    if (S.n_lights == 1)  // (kernel argument: uniform) the light record through scalar loads
+        light_sample<SPH>(S, as_const(S.lights)[0], P, rng, delta, L, lcol);
+    else
+        light_sample<SPH>(S, S.lights[S.sample_light[s]], P, rng, delta, L, lcol);
+    ShadeData sd;
+    int mkind;
+    const bool no_r = hand_decode(S, h1, hp, hs, sd, mkind);
+    return light_sample_color(mkind, sd, L, lcol, no_r);
 }
 
 __device__ __forceinline__ bool shadowed(const Hit &sh) { return sh.prim >= 0 && sh.t > 0 && sh.t < 1; }
@@ -1151,8 +1088,7 @@ __device__ __forceinline__ F3 sample_unshadowed(const DScene &S, const float4 *h
     return sample_unshadowed<PF, SPH>(S, hp[0], hp[hs], hp, hs, s, P, delta);
 }
 
-// FLAT: the flat shadow loop (device_common.h shadow_cast_flat; `mask` is over DScene::sroot records)
-template <int PF, bool SPH = true, bool FLAT = false>
+template <int PF, bool SPH = true>
 __device__ __forceinline__ F3 sample_color(const DScene &S, const float4 &h0, const float4 &h1, const float4 *hp,
                                            size_t hs, uint32_t s, uint64_t mask = ~0ull) {
     F3 P, delta;
@@ -1161,13 +1097,6 @@ __device__ __forceinline__ F3 sample_color(const DScene &S, const float4 &h0, co
     // (the light behind the surface, a black material, an edge-on area light) adds the same
     // nothing to colorFromLights' running sum (+0 + -0 = +0), so its shadow cast is skipped.
     if (c.x == 0.0f && c.y == 0.0f && c.z == 0.0f) return f3(0, 0, 0);
-#ifdef JSRT_X_NOCAST  // (timing experiment only) no shadow cast: every sample unshadowed
-    if (delta.x != 12345.0f) return c;
-#endif
-    if constexpr (FLAT) {
-        if (shadow_cast_flat(S, P, delta, 0.0001, 1, mask)) return f3(0, 0, 0);  // shadowed: contributes +0
-        return c;
-    }
     const Hit sh = world_cast<PF, true>(S, P, delta, 0.0001, 1, false, mask);
     if (shadowed(sh)) return f3(0, 0, 0);  // shadowed: contributes +0
     return c;
@@ -1192,11 +1121,23 @@ __device__ __forceinline__ F3 light_sums(const DScene &S, uint32_t G, F3 ret, F3
     return ret;
 }
 
+// Shadow-root mask of the wave (scene_load.cpp shadow_grid): when every node of the wave has its hit point in
+// one grid cell -- the hand-off is bucketed by cell, so nearly every wave -- the world loop visits only the roots
+// a shadow segment from that cell can meet.  mi = the lane's cell index, in = the lane holds a node.
+__device__ __forceinline__ uint64_t wave_root_mask(const DScene &S, uint32_t mi, bool in) {
+    uint64_t mask = ~0ull;
+    const uint64_t on = __ballot(in);
+    if (on) {
+        const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)mi, __builtin_ctzll(on));
+        if (!__ballot(in && mi != m0) && m0 <= (uint32_t)S.grid_cells) mask = as_const(S.grid_mask)[m0];
+    }
+    return mask;
+}
+
 // STAGE (flat scenes, DScene::stab; not SERIAL): k_shadow's tables (materials, colour constants, light-sample
 // indices) copied into LDS by every block behind its hand-off loads, so a sample's material -> colour chain is
 // LDS round trips
-// FLAT (with STAGE; DScene::n_sroot > 0): the shadow casts through the flat shadow loop (shadow_cast_flat)
-template <int PF, bool CHAIN, bool SERIAL, bool SPH, bool STAGE = false, bool FLAT = false>
+template <int PF, bool CHAIN, bool SERIAL, bool SPH, bool STAGE = false>
 __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADOW_OCC_FLAT : JSRT_SHADOW_OCC) SHADOW_ATTR void k_shadow(
     DScene S, WArgs W, int L) {
     const LevelRange R = CHAIN ? chain_level(W, L) : level_range(W, L);
@@ -1214,19 +1155,8 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADOW_OCC_FLAT : JSR
         q = W.hnode[h];
         mi = f2u(hp[W.hstride].w) & 0xFFu;
     }
-    // Shadow-root mask of the wave (scene_load.cpp shadow_grid): when every node of the wave has its hit
-    // point in one grid cell -- the hand-off is bucketed by cell, so nearly every wave -- the world loop
-    // visits only the roots a shadow segment from that cell can meet.
     uint64_t mask = ~0ull;
-    if (FLAT) mask = S.n_sroot >= 64 ? ~0ull : ((1ull << S.n_sroot) - 1);  // every record
-    if (W.bucket && W.bucket_grid && S.grid_masked) {
-        const uint64_t on = __ballot(in);
-        if (on) {
-            const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)mi, __builtin_ctzll(on));
-            if (!__ballot(in && mi != m0) && m0 <= (uint32_t)S.grid_cells)
-                mask = FLAT ? as_const(S.grid_smask)[m0] : as_const(S.grid_mask)[m0];
-        }
-    }
+    if (W.bucket && W.bucket_grid && S.grid_masked) mask = wave_root_mask(S, mi, in);
     if (CHAIN && !W.bucket && in) q = chain_slot(W, L, q);  // hand-off in level order: the chain's slot
     // Bucketed: every slot below the level's lit total was filled by k_shade with a lit node (DESIGN.md §4.2
     // "lit = in"), so no lane waits for the node record before its sample: only the node's first lane loads it,
@@ -1260,13 +1190,9 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADOW_OCC_FLAT : JSR
     F3 c = f3(0, 0, 0);
     const float4 h0 = hp[0], h1 = hp[W.hstride];  // (loaded by every lane: before the staging barrier)
     if constexpr (STAGE) {
-        extern __shared__ uint4 stab_lds[];
-        const uint4 *src = reinterpret_cast<const uint4 *>(S.stab);
-        for (int k = (int)threadIdx.x; k < S.stab_words_shadow; k += 256) stab_lds[k] = src[k];
-        __syncthreads();
         DScene SL = S;
-        stab_bind(SL, stab_lds, false);
-        if (lit && s < ns) c = sample_color<PF, SPH, FLAT>(SL, h0, h1, hp, W.hstride, s, mask);
+        stab_stage(S, SL, S.stab_words_shadow, false);
+        if (lit && s < ns) c = sample_color<PF, SPH>(SL, h0, h1, hp, W.hstride, s, mask);
     } else {
         if (lit && s < ns) c = sample_color<PF, SPH>(S, h0, h1, hp, W.hstride, s, mask);
     }
@@ -1299,47 +1225,20 @@ __global__ __launch_bounds__(256, JSRT_SHADOW_NODE_OCC) void k_shadow_node(DScen
     const float4 h0 = hp[0], h1 = hp[hs];  // (before the staging barrier)
     const uint32_t tag = f2u(h1.w);
     uint64_t mask = ~0ull;  // the wave's shadow-root mask, as k_shadow's: 64 nodes of (nearly always) one cell
-    if (W.bucket_grid && S.grid_masked) {
-        const uint32_t mi = tag & 0xFFu;
-        const uint64_t on = __ballot(in);
-        if (on) {
-            const uint32_t m0 = (uint32_t)__builtin_amdgcn_readlane((int)mi, __builtin_ctzll(on));
-            if (!__ballot(in && mi != m0) && m0 <= (uint32_t)S.grid_cells) mask = as_const(S.grid_mask)[m0];
-        }
-    }
+    if (W.bucket_grid && S.grid_masked) mask = wave_root_mask(S, tag & 0xFFu, in);
     // (a slot k_shade did not fill -- never, DESIGN.md §4.2 -- must not send the store out of the level: chain
     // slots lie below cap, tree nodes below the level's count)
     const bool lit = in && q < (CHAIN ? W.cap : count);
     const uint32_t i = base + (lit ? q : 0u);
     const float4 nd = W.node[i];  // the ambient and the info word: consumed by the store at the end
-    extern __shared__ uint4 stab_lds[];
-    const uint4 *src = reinterpret_cast<const uint4 *>(S.stab);
-    for (int k = (int)threadIdx.x; k < S.stab_words_shadow; k += 256) stab_lds[k] = src[k];
-    __syncthreads();
-    if (!lit) return;
     DScene SL = S;
-    stab_bind(SL, stab_lds, false);
+    stab_stage(S, SL, S.stab_words_shadow, false);
+    if (!lit) return;
     // per node: the material data of sample_unshadowed, once
     const F3 P = f3(h0.x, h0.y, h0.z);
-    const jsrt_rec_material &M = SL.mat[(tag & HAND_MAT) >> 8];
     ShadeData sd;
-    sd.N = f3(h1.x, h1.y, h1.z);
-    sd.diff = (tag & HAND_DIFF) ? f3(hp[2 * hs].x, hp[2 * hs].y, hp[2 * hs].z) : mc_const3(SL, M.diffuse);
-    sd.spec = (tag & HAND_SPEC) ? f3(hp[4 * hs].x, hp[4 * hs].y, hp[4 * hs].z) : mc_const3(SL, M.specular);
-    sd.R = f3(0, 0, 0);
-    sd.refr = f3(0, 0, 0);
-    sd.kr = 1.0;
-    if (tag & HAND_R) {
-        const float4 h3 = hp[3 * hs];
-        sd.R = f3(h3.x, h3.y, h3.z);
-        if (tag & HAND_KR) {
-            const float4 h5 = hp[5 * hs];
-            sd.refr = f3(h5.x, h5.y, h5.z);
-            sd.kr = __hiloint2double((int)f2u(h3.w), (int)f2u(h5.w));
-        }
-    }
-    sd.smoothness = M.smoothness;
-    const int mkind = (int)M.kind;
+    int mkind;
+    const bool no_r = hand_decode(SL, h1, hp, hs, sd, mkind);
     // per sample: the light sample and its unshadowed colour (sample_unshadowed's per-sample part)
     F3 d[NS], c[NS];
     uint32_t live = 0u;
@@ -1351,7 +1250,7 @@ __global__ __launch_bounds__(256, JSRT_SHADOW_NODE_OCC) void k_shadow_node(DScen
             RngH rng{f2u(h0.w), (uint32_t)SL.sample_call[s]};
             F3 Ld, lcol;
             light_sample<false>(SL, as_const(S.lights)[0], P, rng, d[s], Ld, lcol);
-            c[s] = light_sample_color(mkind, sd, Ld, lcol, !(tag & HAND_R));
+            c[s] = light_sample_color(mkind, sd, Ld, lcol, no_r);
             // (sample_color's skip: a colour of +-0 in every component adds nothing, its cast is not run)
             if (!(c[s].x == 0.0f && c[s].y == 0.0f && c[s].z == 0.0f)) live |= 1u << s;
         }
@@ -1578,45 +1477,45 @@ void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t
         }
         if (W.ns > 0)
             timed(KT_SHADOW, [&] {
-                const hipStream_t st = ss;  // (the launches below name `st`)
                 const size_t ne = ub * (size_t)W.group;
                 if (Q && W.ns <= 64) {
-                    hipLaunchKernelGGL((k_shadow_prep<PF, CHAIN>), dim3(grid_ub(ne)), dim3(256), 0, st, S, W, L);
+                    hipLaunchKernelGGL((k_shadow_prep<PF, CHAIN>), dim3(grid_ub(ne)), dim3(256), 0, ss, S, W, L);
                     if (S.sdf_all_forms)
                         hipLaunchKernelGGL((k_shadow_cast<PF, CHAIN, true>),
-                                           dim3(persistent_grid((const void *)k_shadow_cast<PF, CHAIN, true>, ne)), dim3(256), 0, st, S, W, L);
+                                           dim3(persistent_grid((const void *)k_shadow_cast<PF, CHAIN, true>, ne)), dim3(256), 0, ss, S, W, L);
                     else
                         hipLaunchKernelGGL((k_shadow_cast<PF, CHAIN, false>),
-                                           dim3(persistent_grid((const void *)k_shadow_cast<PF, CHAIN, false>, ne)), dim3(256), 0, st, S, W, L);
-                    hipLaunchKernelGGL((k_shadow_sum<CHAIN>), dim3(grid_ub(ne)), dim3(256), 0, st, S, W, L);
-                } else if (W.ns <= 1 || W.group > 1) {
-                    const dim3 g(grid_ub(ub * (size_t)W.group));
-                    const size_t sl = (size_t)S.stab_words_shadow * 16;  // the LDS-staged tables (flat scenes)
+                                           dim3(persistent_grid((const void *)k_shadow_cast<PF, CHAIN, false>, ne)), dim3(256), 0, ss, S, W, L);
+                    hipLaunchKernelGGL((k_shadow_sum<CHAIN>), dim3(grid_ub(ne)), dim3(256), 0, ss, S, W, L);
+                    return;
+                }
+                const size_t sl = (size_t)S.stab_words_shadow * 16;  // the LDS-staged tables (flat scenes)
+                // k_shadow<SERIAL, SPH, STAGE>: one lane per node or W.group lanes (the grid), the staged tables or
+                // the BVH traversal stack (the dynamic LDS); SPH by the scene's lights
+                auto shadow = [&](auto serial, auto stage) {
+                    constexpr bool SERIAL = decltype(serial)::value, STAGE = decltype(stage)::value;
+                    const dim3 g(grid_ub(SERIAL ? ub : ne));
+                    const size_t l = STAGE ? sl : lds;
+                    if (S.sphere_lights)
+                        hipLaunchKernelGGL((k_shadow<PF, CHAIN, SERIAL, true, STAGE>), g, dim3(256), l, ss, S, W, L);
+                    else
+                        hipLaunchKernelGGL((k_shadow<PF, CHAIN, SERIAL, false, STAGE>), g, dim3(256), l, ss, S, W, L);
+                };
+                constexpr bool FLAT_PF = PF == PF_ANALYTIC;  // only this profile instantiates the staged kernels
+                if (W.ns > 1 && W.group <= 1) {  // SERIAL: more than 64 samples, or JSRT_SHADOW_SERIAL
+                    shadow(std::true_type{}, std::false_type{});
+                } else if (FLAT_PF && sl) {
                     // one lane per lit node (k_shadow_node): a flat scene with staged tables and a bucketed hand-off,
                     // one area light without a Sphere geometry, 2..4 samples; everything else keeps k_shadow
-                    bool node_form = false;
-                    if constexpr (PF == PF_ANALYTIC)
-                        node_form = W.shadow_node && W.bucket && sl && S.n_lights == 1 && !S.sphere_lights && S.n_sroot == 0 &&
-                                    W.ns > 1 && W.ns <= 4;
-                    if (node_form) {
-                        if constexpr (PF == PF_ANALYTIC)
-                            hipLaunchKernelGGL((k_shadow_node<PF, CHAIN, 4>), dim3(grid_ub(ub)), dim3(256), sl, st, S, W, L);
-                    } else if (PF == PF_ANALYTIC && sl && S.sphere_lights && S.n_sroot > 0)
-                        hipLaunchKernelGGL((k_shadow<PF, CHAIN, false, true, PF == PF_ANALYTIC, PF == PF_ANALYTIC>), g, dim3(256), sl, st, S, W, L);
-                    else if (PF == PF_ANALYTIC && sl && S.n_sroot > 0)
-                        hipLaunchKernelGGL((k_shadow<PF, CHAIN, false, false, PF == PF_ANALYTIC, PF == PF_ANALYTIC>), g, dim3(256), sl, st, S, W, L);
-                    else if (PF == PF_ANALYTIC && sl && S.sphere_lights)
-                        hipLaunchKernelGGL((k_shadow<PF, CHAIN, false, true, PF == PF_ANALYTIC>), g, dim3(256), sl, st, S, W, L);
-                    else if (PF == PF_ANALYTIC && sl)
-                        hipLaunchKernelGGL((k_shadow<PF, CHAIN, false, false, PF == PF_ANALYTIC>), g, dim3(256), sl, st, S, W, L);
-                    else if (S.sphere_lights)
-                        hipLaunchKernelGGL((k_shadow<PF, CHAIN, false, true>), g, dim3(256), lds, st, S, W, L);
-                    else
-                        hipLaunchKernelGGL((k_shadow<PF, CHAIN, false, false>), g, dim3(256), lds, st, S, W, L);
-                } else if (S.sphere_lights) {
-                    hipLaunchKernelGGL((k_shadow<PF, CHAIN, true, true>), dim3(grid_ub(ub)), dim3(256), lds, st, S, W, L);
+                    if constexpr (FLAT_PF) {
+                        if (W.shadow_node && W.bucket && S.n_lights == 1 && !S.sphere_lights && W.ns > 1 && W.ns <= 4) {
+                            hipLaunchKernelGGL((k_shadow_node<PF, CHAIN, 4>), dim3(grid_ub(ub)), dim3(256), sl, ss, S, W, L);
+                            return;
+                        }
+                    }
+                    shadow(std::false_type{}, std::bool_constant<FLAT_PF>{});
                 } else {
-                    hipLaunchKernelGGL((k_shadow<PF, CHAIN, true, false>), dim3(grid_ub(ub)), dim3(256), lds, st, S, W, L);
+                    shadow(std::false_type{}, std::false_type{});
                 }
             });
         if (W.ns > 0 && split) (void)hipEventRecord(sync->shadow_done, ss);

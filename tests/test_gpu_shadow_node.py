@@ -9,8 +9,10 @@ The cases: the hybrid chain with grid-cell buckets, a 4-sample area light, side 
 the tree schedule with Fresnel kr / refr planes and two point lights (refraction_path, refraction: the
 multi-light sums); a Sphere area light (heart: the lane-per-sample form under both settings); a mesh profile
 with primitive buckets (bunny); a non-zero ambient term under the node form (cornell_box: Phong walls with
-ambient 0.1, the same area light); and the unbucketed hand-off (JSRT_BUCKET=0), which reads INFO_LIT from the
-node record as before."""
+ambient 0.1, the same area light); the unbucketed hand-off (JSRT_BUCKET=0), which reads INFO_LIT from the
+node record as before; the one-lane-per-node serial k_shadow (JSRT_SHADOW_SERIAL=1) with the bucketed hand-off,
+with a Sphere light and in a BVH profile; and the unstaged analytic k_shade / k_shadow (JSRT_SHADE_LDS=0, read
+when the scene is created)."""
 import numpy as np
 import pytest
 
@@ -30,6 +32,10 @@ CASES = [
     ("refraction", 32, 32, 2, None, 4, {}, {}),
     ("cornell_box", 32, 32, 3, None, 6, {}, {}),
     ("cornell_box_path", 40, 40, 6, 8, 11, {}, {"JSRT_BUCKET": "0"}),
+    ("cornell_box_path", 40, 40, 6, 8, 11, {}, {"JSRT_SHADOW_SERIAL": "1"}),
+    ("heart", 32, 32, 2, None, 5, {}, {"JSRT_SHADOW_SERIAL": "1"}),
+    ("bunny", 48, 40, 2, 4, 3, {}, {"JSRT_SHADOW_SERIAL": "1"}),
+    ("cornell_box_path", 40, 40, 6, 8, 11, {}, {"JSRT_SHADE_LDS": "0"}),
 ]
 
 
