@@ -14,6 +14,7 @@
 
 #include "device_common.h"
 #include "render_kernel.h"
+#include "render_plan.h"
 
 #ifndef JSRT_SHADE_OCC  // min waves per SIMD requested for k_shade: 4 (SDF 167 -> 128 VGPRs) = Menger +5 %, r03_s34
 #define JSRT_SHADE_OCC 4
@@ -190,27 +191,7 @@ __device__ __forceinline__ void write_result(const WArgs &W, uint32_t i, F3 c) {
     }
 }
 
-// patch-ordered owned pixel index -> (owned column c, row py, image column px).  8 x 8-pixel patches in raster order,
-// or (A.tile_p > 0) in raster order within tiles of tile_p x tile_p patches taken in raster order, the last tile
-// row and column partial: the pixels of consecutive indices, and so the rays a batch has in flight, then cover a
-// compact region of the image rather than a band as wide as it (the BVH working set of their casts)
-__device__ __forceinline__ bool pixel_of(const RenderArgs &A, uint32_t p, int &c, int &py, int &px) {
-    int patch = (int)(p >> 6);
-    const int lane = (int)(p & 63);
-    if (A.tile_p > 0) {
-        const int T = A.tile_p, pxn = A.patches_x, pyn = A.patches / A.patches_x;
-        const int ty = patch / (pxn * T), r = patch - ty * pxn * T;  // (every tile row but the last is full)
-        const int h = min(T, pyn - ty * T);
-        const int tx = r / (T * h), r2 = r - tx * T * h;  // (every tile of the row but the last is full)
-        const int w = min(T, pxn - tx * T);
-        patch = (ty * T + r2 / w) * pxn + tx * T + r2 % w;
-    }
-    c = (patch % A.patches_x) * 8 + (lane & 7);
-    py = (patch / A.patches_x) * 8 + (lane >> 3);
-    if (c >= A.ncols || py >= A.H) return false;
-    px = owned_to_px(c, A.x_offset, A.x_delt, A.col_block);
-    return px < A.W;
-}
+// (pixel_of, the patch-ordered owned pixel index -> pixel map of a batch: render_plan.h)
 
 __device__ __forceinline__ F3 pick(bool f, F3 a, F3 b) { return f3(f ? a.x : b.x, f ? a.y : b.y, f ? a.z : b.z); }
 __device__ __forceinline__ Child pick(bool f, const Child &a, const Child &b) {

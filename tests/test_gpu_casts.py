@@ -56,8 +56,7 @@ def test_gpu_cast_dragon_against_oracle(jr):
 
 def test_gpu_cast_menger_inside_against_oracle(jr):
     """SDF_Menger's march from points inside and around the sponge (its holes at every level), against the
-    oracle: the sponge form's early exit (sdf_forms.h sdf_form_runion; JSRT_SDF_EXIT=0 turns it off) must give
-    every distance bit for bit.  The sponge is Mat4.translation([-3.5, 0.5, -3.5]) x rotationY(-0.15) of a
+    oracle: the sponge form's early exit (sdf_forms.h sdf_form_runion) must give every distance bit for bit.  The sponge is Mat4.translation([-3.5, 0.5, -3.5]) x rotationY(-0.15) of a
     unit box (tests/SDF_Menger/test.mjs)."""
     blob = pyoracle.golden_scene("SDF_Menger")
     rng = np.random.default_rng(11)
