@@ -17,6 +17,8 @@
  *   jsrt_material_data  <- World.color(ray, 1) up to Material.color (world.js:31-41, 125-137):
  *                          Geometry.materialData + the world normal / position of each hit
  *   jsrt_sdf_distance   <- SDF.distance (src/sdf.js:53-74) of an SDFGeometry primitive's root
+ *   jsrt_material_color <- MaterialColor.color({UV}) (src/materials.js:20-131) of one colour chain: solid,
+ *                          scaled, checkerboard or texture (TextureMaterialColor.color, :101-130)
  *   jsrt_scene_destroy  <- worker teardown (src/raytrace_launcher.js:106-124 terminate)
  *   jsrt_last_error     <- the reference throws strings (e.g. src/aggregates.js:39); errors here are
  *                          negative return codes + this message, never C++ exceptions.
@@ -166,6 +168,11 @@ int jsrt_material_data(jsrt_scene *scene, const float *rays, size_t n, double *o
 /* SDF.distance (sdf.js:53-74) of the root SDF of SDFGeometry primitive `object` (its OBJS index in the
  * blob) at n points (f32 x 4 in the primitive's local frame, w = 1).  Synchronous. */
 int jsrt_sdf_distance(jsrt_scene *scene, int32_t object, const float *points, size_t n, double *out);
+
+/* MaterialColor.color({UV: uv}) (materials.js:36, 52, 72, 101) of MCOL record `mcolor_index` of the blob -- a
+ * solid, scaled, checkerboard or texture chain -- at n UV pairs (n x 2 f32): out_rgb n x 3 f32, the colour's
+ * first three components (a texture's alpha is not produced).  Synchronous. */
+int jsrt_material_color(jsrt_scene *scene, int32_t mcolor_index, const float *uv, size_t n, float *out_rgb);
 
 /* Number of owned columns for (W, x_offset, x_delt, col_block). */
 int32_t jsrt_owned_columns(int32_t width, int32_t x_offset, int32_t x_delt, int32_t col_block);

@@ -45,14 +45,27 @@
 #define JSRT_SEC_LIGHT JSRT_FOURCC('L', 'I', 'T', 'E')
 #define JSRT_SEC_SDFNODE JSRT_FOURCC('S', 'D', 'F', 'N')
 #define JSRT_SEC_SDFGEOM JSRT_FOURCC('S', 'D', 'F', 'G')
+/* textures (materials.js:77-131 TextureMaterialColor): descriptors and the raw texels they point into.  Both
+ * sections are absent from a scene without textures. */
+#define JSRT_SEC_TEXTURE JSRT_FOURCC('T', 'E', 'X', 'R')
+#define JSRT_SEC_TEXEL JSRT_FOURCC('T', 'E', 'X', 'L')
 
 /* renderer kinds: renderers.js:1 SimpleRenderer, :65 IncrementalMultisamplingRenderer,
  * :47 RandomMultisamplingRenderer */
 enum { JSRT_RENDERER_SIMPLE = 0, JSRT_RENDERER_INCREMENTAL = 1, JSRT_RENDERER_RANDOM = 2 };
 /* camera kinds: cameras.js:18 PerspectiveCamera, :40 DepthOfFieldPerspectiveCamera */
 enum { JSRT_CAMERA_PERSPECTIVE = 0, JSRT_CAMERA_DOF = 1 };
-/* material colours: materials.js:27 Solid, :43 Scaled (number or Vec scale), :63 Checkerboard */
-enum { JSRT_MC_SOLID = 1, JSRT_MC_SCALED_SCALAR = 2, JSRT_MC_SCALED_VEC = 3, JSRT_MC_CHECKER = 4 };
+/* material colours: materials.js:27 Solid, :43 Scaled (number or Vec scale), :63 Checkerboard, :77 Texture
+ * (a = TEXR index) */
+enum {
+    JSRT_MC_SOLID = 1,
+    JSRT_MC_SCALED_SCALAR = 2,
+    JSRT_MC_SCALED_VEC = 3,
+    JSRT_MC_CHECKER = 4,
+    JSRT_MC_TEXTURE = 5
+};
+/* texture modes: materials.js:109 "bilinear", :114 "nearest" */
+enum { JSRT_TEX_BILINEAR = 0, JSRT_TEX_NEAREST = 1 };
 /* materials: materials.js:195 Phong, :294 FresnelPhong, :389 PhongPathTracing, :145 SolidColor,
  * :160 Transparent */
 enum {
@@ -199,6 +212,16 @@ typedef struct { /* SDFG (sdf.js:3-11) */
     float center[4], half[4]; /* root_sdf.getBoundingBox(I, I) */
 } jsrt_rec_sdfgeom;
 
+typedef struct { /* TEXR (materials.js:78-87): _imgdata.width / height, mode, clampU, clampV */
+    uint32_t width, height;
+    uint32_t mode;             /* JSRT_TEX_* */
+    uint32_t clamp_u, clamp_v; /* 0: wrap ((c % 1) + 1) % 1, else Math.clamp(c, 0, 1) */
+    uint32_t pad;
+    uint64_t offset; /* byte offset into TEXL (a multiple of 4) of width * height * 4 bytes: _imgdata.data, RGBA8,
+                        row-major, top row first */
+} jsrt_rec_texture;
+/* TEXL: raw bytes (count = bytes) */
+
 #ifdef __cplusplus
 #define JSRT_STATIC_ASSERT static_assert
 #else
@@ -218,5 +241,6 @@ JSRT_STATIC_ASSERT(sizeof(jsrt_rec_triangle) == 256, "triangle");
 JSRT_STATIC_ASSERT(sizeof(jsrt_rec_light) == 304, "light");
 JSRT_STATIC_ASSERT(sizeof(jsrt_rec_sdfnode) == 336, "sdfnode");
 JSRT_STATIC_ASSERT(sizeof(jsrt_rec_sdfgeom) == 64, "sdfgeom");
+JSRT_STATIC_ASSERT(sizeof(jsrt_rec_texture) == 32, "texture");
 
 #endif

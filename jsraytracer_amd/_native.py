@@ -51,13 +51,15 @@ RC_ABORTED = -4  # jsrt_render_device_progress_ex: the callback asked to stop th
 
 # exported symbols of include/jsrt.h (checked by tests/test_capi_symbols.py)
 EXPORTS = ["jsrt_scene_create", "jsrt_scene_destroy", "jsrt_render", "jsrt_render_device", "jsrt_cast",
-           "jsrt_material_data", "jsrt_sdf_distance", "jsrt_owned_columns", "jsrt_last_error", "jsrt_abi_version",
+           "jsrt_material_data", "jsrt_sdf_distance", "jsrt_material_color", "jsrt_owned_columns", "jsrt_last_error", "jsrt_abi_version",
            "jsrt_device_count", "jsrt_build_id", "jsrt_render_device_progress", "jsrt_render_device_progress_ex",
            "jsrt_render_device_accum", "jsrt_finish_accum"]
 # exported symbols of include/jsrt_mesh.h (native OBJ ingest + BVH build; host-only, no GPU needed)
 MESH_EXPORTS = ["jsrt_blob_attach_obj", "jsrt_blob_attach_obj_mtl", "jsrt_blob_free"]
 # exported symbols of include/jsrt_json.h (Serializer-JSON reader; host-only)
 JSON_EXPORTS = ["jsrt_blob_from_json"]
+# exported symbols of include/jsrt_texture.h (an MCOL record turned into a texture; host-only)
+TEXTURE_EXPORTS = ["jsrt_blob_set_texture"]
 
 
 class MeshOptions(ctypes.Structure):
@@ -156,7 +158,22 @@ def lib():
                                       ctypes.POINTER(JsonInfo)]
     L.jsrt_blob_free.restype = None
     L.jsrt_blob_free.argtypes = [ctypes.c_void_p]
+    # the texture entry points (jsrt_material_color, jsrt_blob_set_texture) are bound where they are called
+    # (texture_api): an A/B library (JSRT_LIB) built from a tree that predates them still loads and renders
     _lib = L
+    return L
+
+
+def texture_api():
+    """The library with jsrt_material_color / jsrt_blob_set_texture bound (JsrtError if it lacks them)."""
+    L = lib()
+    if not hasattr(L, "jsrt_material_color") or not hasattr(L, "jsrt_blob_set_texture"):
+        raise JsrtError(f"{LIB_PATH} has no texture entry points: rebuild it")
+    L.jsrt_material_color.restype = ctypes.c_int
+    L.jsrt_material_color.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.jsrt_blob_set_texture.restype = ctypes.c_int
+    L.jsrt_blob_set_texture.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_void_p] + \
+        [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
     return L
 
 

@@ -15,7 +15,7 @@ OUT = os.path.join(HERE, "_build")
 LIB = os.path.join(OUT, "libjsrt.so")
 PROFILES = {"analytic": 0, "mesh": 9, "sdf": 4, "all": 15}  # device_scene.h PF_ANALYTIC / PF_MESH / PF_SDF / PF_ALL
 HEADERS = ["device_common.h", "fdlibm.h", "js_number.h", "device_scene.h", "render_kernel.h", "render_levels.h", "render_plan.h", "scene_load.h", "sdf_forms.h",
-           "sdf_program.h"]
+           "sdf_program.h", "texture_sample.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("JSRT_OFFLOAD_ARCH", "gfx950")
 
@@ -25,7 +25,7 @@ FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-ffp-contract=off", "-f
          "-Wall", "-Wno-unused-function"]
 
 INCLUDE = os.path.join(HERE, "..", "include")
-PUBLIC = ["jsrt.h", "jsrt_scene.h", "jsrt_mesh.h", "jsrt_json.h"]
+PUBLIC = ["jsrt.h", "jsrt_scene.h", "jsrt_mesh.h", "jsrt_json.h", "jsrt_texture.h"]
 # objects: (object stem, source, extra defines, dependencies); an object is rebuilt only when these change
 UNITS = [("render", "render.hip", [], HEADERS + ["jsrt.h", "jsrt_scene.h"])]
 # each profile in three parts (render_pf.hip JSRT_PART: chain kernels, tree kernels, single-cast entries)
@@ -34,7 +34,8 @@ UNITS += [(f"render_pf{pf}_{part}", "render_pf.hip", [f"-DJSRT_PF={pf}", f"-DJSR
 UNITS += [("capi", "capi.cpp", [], HEADERS + ["jsrt.h", "jsrt_scene.h"]),
           ("scene_load", "scene_load.cpp", [], HEADERS + ["jsrt.h", "jsrt_scene.h"]),
           ("mesh_build", "mesh_build.cpp", [], ["jsrt_mesh.h", "jsrt_scene.h", "obj_parse.h"]),
-          ("json_scene", "json_scene.cpp", [], ["jsrt_json.h", "jsrt_scene.h", "obj_parse.h"])]
+          ("json_scene", "json_scene.cpp", [], ["jsrt_json.h", "jsrt_scene.h", "obj_parse.h"]),
+          ("texture_blob", "texture_blob.cpp", [], ["jsrt_texture.h", "jsrt_scene.h"])]
 OBJ_FLAGS = [f for f in FLAGS if f != "-shared"]
 # No machine-level loop-invariant code motion: it hoists address and f64-constant materialisations out
 # of the light-sample and traversal loops into VGPRs and then spills them (k_shade_lit: 66 spilled

@@ -1747,13 +1747,20 @@ __device__ __forceinline__ void persistent_cast(const DScene &S, uint32_t *ctr, 
 
 // --------------------------------------------------------------------------------------------
 // materials (materials.js)
+}  // namespace jsrt
+#include "texture_sample.h"
+namespace jsrt {
+// TEX: the chain may end in a texture (DScene::has_textures; k_shade's and k_material_color's instantiations).
+// Without it no sampler code is emitted, and a scene with textures never runs such an instantiation on a chain
+// that reaches one (light colours, the only other callers, refuse textures at load).
+template <bool TEX = false>
 __device__ __forceinline__ F3 mc_eval(const DScene &S, int m, float u, float v) {  // MaterialColor.color(data)
     {  // a chain that does not read (u, v): its colour, computed by the loader (scene_load.cpp mc_constants)
         const float4 cc = *reinterpret_cast<const float4 *>(S.mc_const + 4 * m);
         if (cc.w != 0.0f) return f3(cc.x, cc.y, cc.z);
     }
-    // walk Scaled* wrappers (and checkerboard choices) down to the solid colour, then apply the
-    // scales innermost first: ScaledMaterialColor.color = child.color(data).times(scale)
+    // walk Scaled* wrappers (and checkerboard choices) down to the leaf (the solid colour, or a texture), then
+    // apply the scales innermost first: ScaledMaterialColor.color = child.color(data).times(scale)
     auto step = [&](int x) {  // next record below x (checkerboards resolved by (u, v))
         const jsrt_rec_mcolor &M = S.mc[x];
         if (M.kind == JSRT_MC_CHECKER) {  // materials.js:72-75
@@ -1768,12 +1775,15 @@ __device__ __forceinline__ F3 mc_eval(const DScene &S, int m, float u, float v) 
     int n = 0, x = m;  // n = number of Scaled wrappers on the way down
     for (int g = 0; g < 16; ++g) {
         const int k = S.mc[x].kind;
-        if (k == JSRT_MC_SOLID) break;
+        if (k == JSRT_MC_SOLID || (TEX && k == JSRT_MC_TEXTURE)) break;
         if (k != JSRT_MC_CHECKER) ++n;
         x = step(x);
     }
     const jsrt_rec_mcolor &B = S.mc[x];
     F3 c = f3(B.vec[0], B.vec[1], B.vec[2]);
+    if constexpr (TEX) {
+        if (B.kind == JSRT_MC_TEXTURE) tex_sample(S.tex[B.a], S.texels, S.tex_q255, u, v, c.x, c.y, c.z);
+    }
     for (int i = n - 1; i >= 0; --i) {  // the i-th wrapper from the top (usually n <= 1)
         int y = m, seen = 0;
         for (int g = 0; g < 16; ++g) {

@@ -112,7 +112,7 @@ struct DCamera {         // cameras.js:18-53
     int32_t kind, pad[3];
 };
 
-// material flags: MATF_UV colours depend on (u, v) (a checkerboard in some chain); MATF_DIFF_CONST /
+// material flags: MATF_UV colours depend on (u, v) (a checkerboard or a texture in some chain); MATF_DIFF_CONST /
 // MATF_SPEC_CONST the diffuse / specular chain is a constant (mc_const); MATF_SPEC_ZERO the specular colour
 // is the constant (+0, +0, +0) and the smoothness in [0, 1e5] (render_levels.h: no specular power)
 enum { MATF_UV = 1, MATF_DIFF_CONST = 2, MATF_SPEC_CONST = 4, MATF_SPEC_ZERO = 8 };
@@ -173,6 +173,13 @@ struct DScene {
     const void *stab;            // 16-B aligned
     int32_t stab_words, stab_words_shadow;
     int32_t stab_off[12];
+    // Textures (materials.js:77-131; texture_sample.h): the blob's TEXR descriptors and TEXL bytes, and the 256
+    // quotients byte / 255.  has_textures: some MCOL record is a texture, so k_shade runs its TEX instantiation
+    // (a scene without one launches kernels whose code holds no sampler).  Texels stay in global memory.
+    const jsrt_rec_texture *tex;
+    const uint8_t *texels;
+    const double *tex_q255;
+    int32_t has_textures, pad_tex;
 };
 enum {  // DScene::stab tables, in image order: k_shadow's first (mat .. sample_light), then k_shade's
     STAB_MAT, STAB_MAT_FLAGS, STAB_MC, STAB_MC_CONST, STAB_SAMPLE_CALL, STAB_SAMPLE_LIGHT,

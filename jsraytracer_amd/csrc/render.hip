@@ -539,6 +539,24 @@ hipError_t sdf_distance_points(const DScene &S, int g, const float *d_pts, uint3
     return hipGetLastError();
 }
 
+// MaterialColor.color({UV: uv}) of one MCOL record (solid, scaled, checkerboard or texture chain), one lane per
+// UV pair: mc_eval with the sampler, as k_shade's TEX instantiation runs it (jsrt_material_color)
+__global__ __launch_bounds__(256) void k_material_color(DScene S, int mc, const float *uv, uint32_t n, float *rgb) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const F3 c = mc_eval<true>(S, mc, uv[2 * (size_t)i], uv[2 * (size_t)i + 1]);
+    float *o = rgb + 3 * (size_t)i;
+    o[0] = c.x;
+    o[1] = c.y;
+    o[2] = c.z;
+}
+
+hipError_t material_color_uvs(const DScene &S, int mc, const float *d_uv, uint32_t n, float *d_rgb, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_material_color, dim3(grid_ub(n)), dim3(256), 0, st, S, mc, d_uv, n, d_rgb);
+    return hipGetLastError();
+}
+
 hipError_t cast_rays(const DScene &S, const float *d_rays, uint32_t n, double min_dist, double max_dist, bool transparent,
                      double *d_t, int32_t *d_prim, hipStream_t st) {
     if (n == 0) return hipSuccess;

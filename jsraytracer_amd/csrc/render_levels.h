@@ -445,7 +445,7 @@ __device__ __forceinline__ void surface_data(const DScene &S, const Hit &h, F3 o
 // bit 31 = scattered about -N, the refraction side; 0 = none) and the node's N.  k_shade recomputes those
 // directions at its tail (fix_child_dirs), so nothing of it is live in registers through the stores.
 constexpr uint32_t INFO_FIX = 1u << 30;
-template <int PF>
+template <int PF, bool TEX>
 __device__ __forceinline__ int shade_node(const DScene &S, bool lit, const Hit &h, F3 o, F3 d, uint32_t addr,
                                           uint32_t key, NodeOut &out, Child &ch0, Child &ch1, uint32_t *fixl,
                                           bool force_fix) {
@@ -463,7 +463,7 @@ __device__ __forceinline__ int shade_node(const DScene &S, bool lit, const Hit &
     const int mkind = (int)M.kind;
     Rng rng{key, addr, 0};
     if (mkind == JSRT_MAT_SOLID) {
-        out.surf = mc_eval(S, M.color, u, v);
+        out.surf = mc_eval(S, M.color, u, v);  // (no texture here or in the slots below without <TEX>: refused at load)
         out.info = INFO_HIT;
         return 0;
     }
@@ -486,9 +486,9 @@ __device__ __forceinline__ int shade_node(const DScene &S, bool lit, const Hit &
     sd.N = Nn;
     sd.vdotn = vdotn;
     sd.R = normalized(sub(scale(Nn, 2 * vdotn), sd.V));
-    sd.ambient = mul(basecolor, mc_eval(S, M.ambient, u, v));
-    sd.diff = mul(basecolor, mc_eval(S, M.diffuse, u, v));
-    sd.spec = mc_eval(S, M.specular, u, v);
+    sd.ambient = mul(basecolor, mc_eval<TEX>(S, M.ambient, u, v));
+    sd.diff = mul(basecolor, mc_eval<TEX>(S, M.diffuse, u, v));
+    sd.spec = mc_eval<TEX>(S, M.specular, u, v);
     sd.refl = mc_eval(S, M.reflect, u, v);
     sd.trans = mc_eval(S, M.transmit, u, v);
     sd.smoothness = M.smoothness;
@@ -826,7 +826,11 @@ __device__ __forceinline__ void stab_stage(const DScene &S, DScene &SL, int word
 
 // STAGE (flat scenes whose shading tables fit, DScene::stab): the tables are copied into LDS by every block, so a
 // hit's dependent record chain (prim -> shading matrix / material -> colour constants) is LDS round trips
-template <int PF, bool CHAIN, bool STAGE>
+// TEX (a scene with textures, DScene::has_textures): the colour chains may end in a texture (mc_eval<true>,
+// texture_sample.h).  A template parameter of the kernel, so the instantiations every other scene launches hold no
+// sampler and keep their registers (profiles/texture_kernel_resources.txt; the same body behind a forceinline
+// wrapper cost k_shade<PF_ANALYTIC, false, false> a VGPR and the SDF chain two spills).
+template <int PF, bool CHAIN, bool STAGE, bool TEX = false>
 __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
                                                     : (PF & PF_SDF) ? JSRT_SHADE_OCC_SDF : JSRT_SHADE_OCC) SHADE_ATTR void k_shade(
     DScene S, WArgs W, int L, int child_depth) {
@@ -883,7 +887,7 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
             rkey = W.key[r];
         }
         const Hit h{rt, prim, rctx};
-        nchild = shade_node<PF>(SL, W.ns > 0, h, ro, rd, raddr, rkey, out, ch0, ch1, fixl, W.force_fix != 0);
+        nchild = shade_node<PF, TEX>(SL, W.ns > 0, h, ro, rd, raddr, rkey, out, ch0, ch1, fixl, W.force_fix != 0);
         out.h.node = CHAIN ? slot : q;  // (k_shadow: node base + this)
         out.h.mask = (uint32_t)S.grid_cells;  // every root
         if (W.bucket && (out.info & INFO_LIT)) {  // the lit node's hand-off slot, ranked by k_extend
@@ -1007,6 +1011,7 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
         W.prim[rr] = -1;
     }
 }
+
 
 // The light samples of the lit nodes of level L (lights.js sampleIterator), their shadow casts
 // (materials.js:250-252), colorFromLightSample (materials.js:261-269, 340-356) and the
@@ -1445,9 +1450,15 @@ void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t
         if (W.bucket) hipLaunchKernelGGL(k_bucket_offsets, dim3(1), dim3(256), 0, st, W, L);
         if (split && L > 0 && W.ns > 0) (void)hipStreamWaitEvent(st, sync->shadow_done, 0);  // the hand-off is free
         timed(KT_SHADE, [&] {
-            if (PF == PF_ANALYTIC && S.stab_words > 0)  // the LDS-staged shading tables
-                hipLaunchKernelGGL((k_shade<PF, CHAIN, PF == PF_ANALYTIC>), dim3(grid_ub(ub)), dim3(256), (size_t)S.stab_words * 16,
-                                   st, S, W, L, child_depth);
+            const bool staged = PF == PF_ANALYTIC && S.stab_words > 0;  // the LDS-staged shading tables
+            const size_t sl = staged ? (size_t)S.stab_words * 16 : 0;
+            if (S.has_textures) {  // the TEX instantiations: the texture sampler in the colour chains
+                if (staged)
+                    hipLaunchKernelGGL((k_shade<PF, CHAIN, PF == PF_ANALYTIC, true>), dim3(grid_ub(ub)), dim3(256), sl, st, S, W, L, child_depth);
+                else
+                    hipLaunchKernelGGL((k_shade<PF, CHAIN, false, true>), dim3(grid_ub(ub)), dim3(256), 0, st, S, W, L, child_depth);
+            } else if (staged)
+                hipLaunchKernelGGL((k_shade<PF, CHAIN, PF == PF_ANALYTIC>), dim3(grid_ub(ub)), dim3(256), sl, st, S, W, L, child_depth);
             else
                 hipLaunchKernelGGL((k_shade<PF, CHAIN, false>), dim3(grid_ub(ub)), dim3(256), 0, st, S, W, L, child_depth);
             if (child_depth > 0) hipLaunchKernelGGL(k_fix_dirs, dim3(1), dim3(256), 0, st, W);

@@ -29,6 +29,9 @@ struct Blob {
     const jsrt_rec_light *lite = nullptr;
     const jsrt_rec_sdfnode *sdf = nullptr;
     const jsrt_rec_sdfgeom *sdfg = nullptr;
+    const jsrt_rec_texture *tex = nullptr;
+    const uint8_t *texl = nullptr;
+    uint32_t n_tex = 0, n_texl = 0;
     uint32_t n_mc = 0, n_mat = 0, n_geom = 0, n_obj = 0, n_mats = 0, n_root = 0, n_chld = 0, n_bvh = 0, n_tri = 0,
              n_lite = 0, n_sdf = 0, n_sdfg = 0;
 };
@@ -74,6 +77,8 @@ Blob parse(const void *data, size_t nbytes) {
         case JSRT_SEC_LIGHT: bind(s, b, B.lite, B.n_lite, "LITE"); break;
         case JSRT_SEC_SDFNODE: bind(s, b, B.sdf, B.n_sdf, "SDFN"); break;
         case JSRT_SEC_SDFGEOM: bind(s, b, B.sdfg, B.n_sdfg, "SDFG"); break;
+        case JSRT_SEC_TEXTURE: bind(s, b, B.tex, B.n_tex, "TEXR"); break;
+        case JSRT_SEC_TEXEL: bind(s, b, B.texl, B.n_texl, "TEXL"); break;
         default: break;  // unknown sections are ignored (forward compatible)
         }
     }
@@ -221,16 +226,43 @@ struct Loader {
             check_mc(m.a, depth + 1);
             break;
         case JSRT_MC_CHECKER: check_mc(m.a, depth + 1); check_mc(m.b, depth + 1); break;
+        case JSRT_MC_TEXTURE: {  // materials.js:77-87: a descriptor whose texels lie inside TEXL
+            if (m.a < 0 || (uint32_t)m.a >= B.n_tex) fail("texture index out of range");
+            const jsrt_rec_texture &T = B.tex[m.a];
+            if (T.width < 1 || T.height < 1) fail("texture width and height must be at least 1");
+            if (T.mode != JSRT_TEX_BILINEAR && T.mode != JSRT_TEX_NEAREST) fail("unsupported texture mode");
+            // width * height * 4 bytes from offset lie inside TEXL (texels < 2^64: the comparison cannot overflow)
+            if (T.offset % 4 || T.offset > B.n_texl || (uint64_t)T.width * T.height > ((uint64_t)B.n_texl - T.offset) / 4)
+                fail("texture texels out of range of the texel section");
+            break;
+        }
         default: fail("unsupported material colour kind");
         }
     }
 
-    bool mc_uses_uv(int32_t i, int depth = 0) {
+    bool mc_uses_uv(int32_t i, int depth = 0) {  // a UV-reading leaf (checkerboard, texture) in the chain
         if (i < 0 || (uint32_t)i >= B.n_mc || depth > 8) return false;
         const jsrt_rec_mcolor &m = B.mc[i];
-        if (m.kind == JSRT_MC_CHECKER) return true;
+        if (m.kind == JSRT_MC_CHECKER || m.kind == JSRT_MC_TEXTURE) return true;
         if (m.kind == JSRT_MC_SCALED_SCALAR || m.kind == JSRT_MC_SCALED_VEC) return mc_uses_uv(m.a, depth + 1);
         return false;
+    }
+
+    bool mc_has_texture(int32_t i, int depth = 0) {  // a texture reachable from the chain (checked chains only)
+        if (i < 0 || (uint32_t)i >= B.n_mc || depth > 8) return false;
+        const jsrt_rec_mcolor &m = B.mc[i];
+        if (m.kind == JSRT_MC_TEXTURE) return true;
+        if (m.kind == JSRT_MC_CHECKER) return mc_has_texture(m.a, depth + 1) || mc_has_texture(m.b, depth + 1);
+        if (m.kind == JSRT_MC_SCALED_SCALAR || m.kind == JSRT_MC_SCALED_VEC) return mc_has_texture(m.a, depth + 1);
+        return false;
+    }
+
+    // A texture's colour has four components in the reference (Vec.from([r, g, b, a]), materials.js:129); the
+    // kernels carry three.  It is accepted only where the reference drops the fourth before anything reads it
+    // (DESIGN.md §2.6); everywhere else the texel alpha would change the reference's result, so the scene is refused.
+    void refuse_texture(int32_t chain, const char *owner, const char *slot, const char *why) {
+        if (mc_has_texture(chain))
+            fail(std::string("TextureMaterialColor is not supported in ") + owner + "." + slot + ": " + why);
     }
 
     void shading_matrices() {
@@ -938,11 +970,21 @@ struct Loader {
         for (uint32_t i = 0; i < B.n_mat; ++i) {
             const jsrt_rec_material &M = B.mat[i];
             if (M.kind < JSRT_MAT_PHONG || M.kind > JSRT_MAT_TRANSPARENT) fail("unsupported material kind");
-            if (M.kind == JSRT_MAT_SOLID || M.kind == JSRT_MAT_TRANSPARENT) check_mc(M.color);
-            else {
+            static const char *const kind_name[] = {"", "PhongMaterial", "FresnelPhongMaterial", "PhongPathTracingMaterial",
+                                                    "SolidColorMaterial", "TransparentMaterial"};
+            const char *kn = kind_name[M.kind];
+            if (M.kind == JSRT_MAT_SOLID || M.kind == JSRT_MAT_TRANSPARENT) {
+                check_mc(M.color);
+                refuse_texture(M.color, kn, "color", "the colour goes to World.color and setColor, which read its alpha");
+            } else {
                 check_mc(M.ambient); check_mc(M.diffuse); check_mc(M.specular); check_mc(M.reflect); check_mc(M.transmit);
                 if (M.ambient < 0 || M.diffuse < 0 || M.specular < 0 || M.reflect < 0 || M.transmit < 0)
                     fail("Phong material lacks a colour");
+                refuse_texture(M.reflect, kn, "reflectivity", "squarednorm() > 0 would count the texel alpha (materials.js:277)");
+                refuse_texture(M.transmit, kn, "transmissivity", "squarednorm() > 0 would count the texel alpha (materials.js:284)");
+                if (M.kind == JSRT_MAT_PATH)
+                    refuse_texture(M.specular, kn, "specularity",
+                                   "average() and the scattered child colour would read the texel alpha (materials.js:403, 411)");
                 if (M.kind == JSRT_MAT_PATH && !isfinite(M.smoothness))
                     fail("infinite-smoothness path-tracing scatter is broken in the reference (materials.js:430)");
             }
@@ -952,7 +994,18 @@ struct Loader {
                 if (mc_uses_uv(root)) fl |= MATF_UV;
             S.mat_flags.push_back(fl);
         }
-        for (uint32_t i = 0; i < B.n_mc; ++i) S.mc.push_back(B.mc[i]);
+        for (uint32_t i = 0; i < B.n_mc; ++i) {
+            S.mc.push_back(B.mc[i]);
+            if (B.mc[i].kind == JSRT_MC_TEXTURE) {  // (a record no material uses is checked too: jsrt_material_color)
+                check_mc((int32_t)i);
+                S.has_textures = 1;
+            }
+        }
+        if (S.has_textures) {  // descriptors and texels as they are in the blob (texels stay in global memory)
+            S.tex.assign(B.tex, B.tex + B.n_tex);
+            S.texels.assign(B.texl, B.texl + B.n_texl);
+            for (int b = 0; b < 256; ++b) S.tex_q255.push_back((double)b / 255.0);  // `data[i] / 255`, correctly rounded
+        }
         mc_constants();
         // constant diffuse / specular colours (k_shadow reads them from mc_const, not the hand-off)
         for (size_t i = 0; i < S.mat.size(); ++i) {
@@ -997,6 +1050,8 @@ struct Loader {
             d.kind = (int32_t)L.kind;
             d.color = L.color;
             check_mc(L.color);
+            refuse_texture(L.color, L.kind == JSRT_LIGHT_AREA ? "RandomSampleAreaLight" : "SimplePointLight", "color",
+                           "light colours keep all four components");
             for (int32_t m = L.color, g = 0; m >= 0 && g < 16; ++g) {  // checkerboard anywhere in the chain?
                 const jsrt_rec_mcolor &mc = B.mc[m];
                 if (mc.kind == JSRT_MC_CHECKER) { d.needs_uv = 1; break; }
@@ -1054,6 +1109,8 @@ struct Loader {
                 } else if (c.kind == JSRT_MC_CHECKER) {
                     todo.push_back(c.a);
                     todo.push_back(c.b);
+                } else if (c.kind == JSRT_MC_TEXTURE) {
+                    return true;  // (refused in the slots this is asked about; never called constant)
                 } else todo.push_back(c.a);
             }
             return !todo.empty();

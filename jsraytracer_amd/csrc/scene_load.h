@@ -29,6 +29,10 @@ struct HostScene {
     std::vector<double> shade0, shadeI;  // 16 per slot / per ctx: precomputed shading matrices
     std::vector<jsrt_rec_mcolor> mc;
     std::vector<float> mc_const;        // 4 per mc record: its colour when UV-independent (w = 1), else w = 0
+    int32_t has_textures = 0;           // some MCOL record is a texture (the kernels' TEX instantiations)
+    std::vector<jsrt_rec_texture> tex;  // the blob's TEXR descriptors ...
+    std::vector<uint8_t> texels;        // ... and TEXL bytes (empty without textures)
+    std::vector<double> tex_q255;       // byte / 255 (texture_sample.h tex_q255_table; empty without textures)
     std::vector<DLight> lights;
     std::vector<int32_t> sample_light, sample_call;  // per light sample of a node
     int32_t light_draws = 0;

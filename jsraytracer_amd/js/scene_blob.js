@@ -16,13 +16,14 @@
 
 const SEC = {};
 function fourcc(s) { return s.charCodeAt(0) | (s.charCodeAt(1) << 8) | (s.charCodeAt(2) << 16) | (s.charCodeAt(3) << 24) >>> 0; }
-for (const t of ["RNDR", "CAMR", "MCOL", "MATL", "GEOM", "OBJS", "MATS", "ROOT", "CHLD", "BVHN", "TRIS", "LITE", "SDFN", "SDFG"])
+for (const t of ["RNDR", "CAMR", "MCOL", "MATL", "GEOM", "OBJS", "MATS", "ROOT", "CHLD", "BVHN", "TRIS", "LITE", "SDFN", "SDFG", "TEXR", "TEXL"])
     SEC[t] = fourcc(t) >>> 0;
 
 const K = {
     RENDERER_SIMPLE: 0, RENDERER_INCREMENTAL: 1, RENDERER_RANDOM: 2,
     CAMERA_PERSPECTIVE: 0, CAMERA_DOF: 1,
-    MC_SOLID: 1, MC_SCALED_SCALAR: 2, MC_SCALED_VEC: 3, MC_CHECKER: 4,
+    MC_SOLID: 1, MC_SCALED_SCALAR: 2, MC_SCALED_VEC: 3, MC_CHECKER: 4, MC_TEXTURE: 5,
+    TEX_BILINEAR: 0, TEX_NEAREST: 1,
     MAT_PHONG: 1, MAT_FRESNEL: 2, MAT_PATH: 3, MAT_SOLID: 4, MAT_TRANSPARENT: 5,
     GEOM_PLANE: 1, GEOM_SQUARE: 2, GEOM_CIRCLE: 3, GEOM_SPHERE: 4, GEOM_CYLINDER: 5, GEOM_AABB: 6,
     GEOM_TRIANGLE: 7, GEOM_SDF: 8,
@@ -82,7 +83,12 @@ class SceneBlobWriter {
     constructor() {
         this.sec = {};
         for (const t of Object.keys(REC_SIZE)) this.sec[t] = [];
-        this.maps = { mc: new Map(), mat: new Map(), geom: new Map(), obj: new Map(), bvh: new Map(), matrix: new Map(),
+        // textures (TEXR descriptors + TEXL texel bytes): sections written only when a scene has one, so a scene
+        // without textures exports byte for byte as before
+        this.textures = [];
+        this.texels = [];
+        this.texelBytes = 0;
+        this.maps = { tex: new Map(), mc: new Map(), mat: new Map(), geom: new Map(), obj: new Map(), bvh: new Map(), matrix: new Map(),
                       matrixBytes: new Map(), sdf: new Map(), sdfgeom: new Map() };
     }
     push(tag, rec) { this.sec[tag].push(rec); return this.sec[tag].length - 1; }
@@ -119,10 +125,35 @@ class SceneBlobWriter {
             }
         } else if (isA(mc, "CheckerboardMaterialColor")) {
             r.u32(0, K.MC_CHECKER).i32(4, this.mcIndex(mc.color1)).i32(8, this.mcIndex(mc.color2));
+        } else if (isA(mc, "TextureMaterialColor")) {
+            r.u32(0, K.MC_TEXTURE).i32(4, this.texIndex(mc)).i32(8, -1);
         } else
             throw "scene_blob: unsupported MaterialColor " + (mc.constructor && mc.constructor.name);
         const idx = this.push("MCOL", r);
         this.maps.mc.set(mc, idx);
+        return idx;
+    }
+
+    // TextureMaterialColor (materials.js:77-87): one TEXR descriptor per distinct object, its ImageData bytes
+    // (RGBA8, row-major, top row first) appended to TEXL
+    texIndex(mc) {
+        if (this.maps.tex.has(mc)) return this.maps.tex.get(mc);
+        const img = mc._imgdata;
+        const w = img && img.width, h = img && img.height;
+        if (!(Number.isInteger(w) && Number.isInteger(h) && w >= 1 && h >= 1) || !img.data || img.data.length !== w * h * 4)
+            throw "scene_blob: TextureMaterialColor._imgdata is not a width x height RGBA8 image";
+        if (mc.width !== w || mc.height !== h) throw "scene_blob: TextureMaterialColor size differs from its image";
+        let mode;
+        if (mc.mode === "bilinear") mode = K.TEX_BILINEAR;
+        else if (mc.mode === "nearest") mode = K.TEX_NEAREST;
+        else throw "scene_blob: unsupported texture mode " + mc.mode;
+        const r = new Rec(32);
+        r.u32(0, w).u32(4, h).u32(8, mode).u32(12, mc.clampU ? 1 : 0).u32(16, mc.clampV ? 1 : 0).u32(20, 0);
+        r.u32(24, this.texelBytes % 4294967296).u32(28, Math.floor(this.texelBytes / 4294967296));
+        this.texels.push(Buffer.from(Uint8Array.from(img.data)));
+        this.texelBytes += w * h * 4;
+        const idx = this.textures.push(r) - 1;
+        this.maps.tex.set(mc, idx);
         return idx;
     }
 
@@ -345,7 +376,8 @@ class SceneBlobWriter {
 
     serialize() {
         const tags = Object.keys(REC_SIZE);
-        const header = 16 + 24 * tags.length;
+        const ntex = this.textures.length;
+        const header = 16 + 24 * (tags.length + (ntex ? 2 : 0));
         let off = (header + 7) & ~7;
         const descs = [];
         for (const t of tags) {
@@ -353,10 +385,12 @@ class SceneBlobWriter {
             descs.push([t, this.sec[t].length, off, bytes]);
             off += (bytes + 7) & ~7;
         }
+        const texr = off, texl = texr + 32 * ntex;
+        if (ntex) off = texl + ((this.texelBytes + 7) & ~7);
         const out = Buffer.alloc(off);
         out.writeUInt32LE(0x5452534A, 0);
         out.writeUInt32LE(1, 4);
-        out.writeUInt32LE(tags.length, 8);
+        out.writeUInt32LE(tags.length + (ntex ? 2 : 0), 8);
         out.writeUInt32LE(0, 12);
         descs.forEach(([t, n, o, b], i) => {
             const p = 16 + 24 * i;
@@ -367,6 +401,16 @@ class SceneBlobWriter {
             let q = o;
             for (const rec of this.sec[t]) { Buffer.from(rec.buf).copy(out, q); q += REC_SIZE[t]; }
         });
+        if (ntex) {
+            const u64 = (v, p) => { out.writeUInt32LE(v % 4294967296, p); out.writeUInt32LE(Math.floor(v / 4294967296), p + 4); };
+            let p = 16 + 24 * tags.length;
+            out.writeUInt32LE(SEC.TEXR, p); out.writeUInt32LE(ntex, p + 4); u64(texr, p + 8); u64(32 * ntex, p + 16);
+            p += 24;
+            out.writeUInt32LE(SEC.TEXL, p); out.writeUInt32LE(this.texelBytes, p + 4); u64(texl, p + 8); u64(this.texelBytes, p + 16);
+            this.textures.forEach((rec, i) => Buffer.from(rec.buf).copy(out, texr + 32 * i));
+            let q = texl;
+            for (const b of this.texels) { b.copy(out, q); q += b.length; }
+        }
         return out;
     }
 }

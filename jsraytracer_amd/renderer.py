@@ -100,6 +100,15 @@ class Scene:
               "jsrt_sdf_distance")
         return out
 
+    def material_color(self, mcolor, uv):
+        """MaterialColor.color({UV}) of MCOL record `mcolor` (a solid, scaled, checkerboard or texture chain) at
+        uv (n x 2 f32) on the device (include/jsrt.h jsrt_material_color): n x 3 f32, r g b."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.empty((len(uv), 3), np.float32)
+        check(_native.texture_api().jsrt_material_color(self._h, int(mcolor), uv.ctypes.data, len(uv), out.ctypes.data),
+              "jsrt_material_color")
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             _native.lib().jsrt_scene_destroy(self._h)
@@ -227,6 +236,32 @@ def scene_header(blob):
             kind, spp, depth, w, h = struct.unpack_from("<5I", blob, off)
             return {"kind": kind, "spp": spp, "max_depth": depth, "width": w, "height": h}
     raise JsrtError("scene blob has no renderer record")
+
+
+TEXTURE_MODES = {"bilinear": 0, "nearest": 1}  # include/jsrt_scene.h JSRT_TEX_*
+
+
+def set_texture(blob, mcolor, image, mode="bilinear", clampU=True, clampV=True):
+    """A copy of `blob` in which MCOL record `mcolor` is TextureMaterialColor(image, mode, clampU, clampV)
+    (materials.js:78-87; include/jsrt_texture.h jsrt_blob_set_texture): the way to texture a scene that came from
+    JSON or OBJ ingest.  image: (H, W, 4) uint8, ImageData order (RGBA, top row first).  Host-only; whether the
+    slots the record sits in accept a texture is decided by Scene(...)."""
+    if mode not in TEXTURE_MODES:
+        raise JsrtError(f"unsupported texture mode {mode!r}")
+    image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 4:
+        raise JsrtError("image must be an (H, W, 4) uint8 array")
+    image = np.ascontiguousarray(image)
+    blob = bytes(blob)
+    L = _native.texture_api()
+    out, n = ctypes.c_void_p(), ctypes.c_size_t()
+    check(L.jsrt_blob_set_texture(blob, len(blob), int(mcolor), image.ctypes.data, image.shape[1], image.shape[0],
+                                  TEXTURE_MODES[mode], int(bool(clampU)), int(bool(clampV)), ctypes.byref(out),
+                                  ctypes.byref(n)), "jsrt_blob_set_texture")
+    try:
+        return ctypes.string_at(out, n.value)
+    finally:
+        L.jsrt_blob_free(out)
 
 
 class HipRenderer:
