@@ -169,6 +169,18 @@ int jsrt_material_data(jsrt_scene *scene, const float *rays, size_t n, double *o
  * blob) at n points (f32 x 4 in the primitive's local frame, w = 1).  Synchronous. */
 int jsrt_sdf_distance(jsrt_scene *scene, int32_t object, const float *points, size_t n, double *out);
 
+/* What the loader decided for the SDFGeometry primitives of a scene blob, in the blob's primitive order: per
+ * primitive its OBJS index and the form of its root SDF's program (sdf_program.h SFORM_*: straight-line device
+ * code; 0 = the program VM runs it), the first `cap` of them; *count = how many there are; *all_forms = 1 when
+ * there is at least one and every root is a form (the persistent marches then carry no VM).  Any of all_forms,
+ * objects and forms may be NULL.  jsrt_sdf_forms loads the blob on the host (no GPU needed) and fails as
+ * jsrt_scene_create would for a tree the loader refuses; jsrt_scene_sdf_forms reports what `scene` was loaded
+ * with (the load-time A/B knobs are read once, at jsrt_scene_create). */
+int jsrt_sdf_forms(const void *blob, size_t nbytes, int32_t *all_forms, int32_t *objects, int32_t *forms, size_t cap,
+                   size_t *count);
+int jsrt_scene_sdf_forms(jsrt_scene *scene, int32_t *all_forms, int32_t *objects, int32_t *forms, size_t cap,
+                         size_t *count);
+
 /* MaterialColor.color({UV: uv}) (materials.js:36, 52, 72, 101) of MCOL record `mcolor_index` of the blob -- a
  * solid, scaled, checkerboard or texture chain -- at n UV pairs (n x 2 f32): out_rgb n x 3 f32, the colour's
  * first three components (a texture's alpha is not produced).  Synchronous. */

@@ -11,9 +11,10 @@
  *
  * The scene the JSON was written from is restored where the reference's own round trip loses it
  * (SURVEY.md §8(f)3): JSON null is read back as +Infinity in BoxSDF.size, AABB half sizes and
- * refractiveIndexRatio and as NaN in matrices (any other null is an error); classes are taken from
- * `_t` (PhongPathTracingMaterial.deserialize would build a FresnelPhongMaterial, materials.js:394-396);
- * and Triangle per-vertex normals / UVs, which Triangle.serialize drops (geometry.js:355-357), come
+ * refractiveIndexRatio, and as NaN in matrices and in an SDFGeometry's AABB centre (an unbounded box moved
+ * by a matrix, geometry.js:94-105; a null half size on such an axis is -Infinity); any other null is an
+ * error.  Classes are taken from `_t` (PhongPathTracingMaterial.deserialize would build a
+ * FresnelPhongMaterial, materials.js:394-396); and Triangle per-vertex normals / UVs, which Triangle.serialize drops (geometry.js:355-357), come
  * from the `psdata_obj` side-channel: the OBJ text(s) the meshes were loaded from, NUL-separated,
  * matched per triangle on its vertex positions.  NULL / 0: no side-channel (face normals, as the
  * reference renders its deserialized scene).

@@ -53,7 +53,7 @@ RC_ABORTED = -4  # jsrt_render_device_progress_ex: the callback asked to stop th
 EXPORTS = ["jsrt_scene_create", "jsrt_scene_destroy", "jsrt_render", "jsrt_render_device", "jsrt_cast",
            "jsrt_material_data", "jsrt_sdf_distance", "jsrt_material_color", "jsrt_owned_columns", "jsrt_last_error", "jsrt_abi_version",
            "jsrt_device_count", "jsrt_build_id", "jsrt_render_device_progress", "jsrt_render_device_progress_ex",
-           "jsrt_render_device_accum", "jsrt_finish_accum"]
+           "jsrt_render_device_accum", "jsrt_finish_accum", "jsrt_sdf_forms", "jsrt_scene_sdf_forms"]
 # exported symbols of include/jsrt_mesh.h (native OBJ ingest + BVH build; host-only, no GPU needed)
 MESH_EXPORTS = ["jsrt_blob_attach_obj", "jsrt_blob_attach_obj_mtl", "jsrt_blob_free"]
 # exported symbols of include/jsrt_json.h (Serializer-JSON reader; host-only)
@@ -139,6 +139,12 @@ def lib():
     L.jsrt_material_data.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 7
     L.jsrt_sdf_distance.restype = ctypes.c_int
     L.jsrt_sdf_distance.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.jsrt_sdf_forms.restype = ctypes.c_int
+    L.jsrt_sdf_forms.argtypes = [ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 3 + \
+        [ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    L.jsrt_scene_sdf_forms.restype = ctypes.c_int
+    L.jsrt_scene_sdf_forms.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 3 + \
+        [ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     L.jsrt_owned_columns.restype = ctypes.c_int32
     L.jsrt_owned_columns.argtypes = [ctypes.c_int32] * 4
     L.jsrt_last_error.restype = ctypes.c_char_p

@@ -934,11 +934,16 @@ __device__ __forceinline__ SdfMD sdf_material(const DScene &S, int root, F3 p, c
         int stage;     // 0: evaluating child a, 1: evaluating child b
         SdfMD a;
     };
-    Pending stk[8];
+    // The host admits only trees whose walk fits both bounds (scene_load.cpp check_sdf_material: at most
+    // SDF_MAX_BLEND pending blends, at most SDF_MAX_MD_STEPS node visits), so neither early exit below is taken.
+    Pending stk[SDF_MAX_BLEND];
     int sp = 0;
     int n = root;
-    SdfMD res;
-    for (int guard = 0; guard < 256; ++guard) {
+    SdfMD res;  // defined on every exit: no basecolor, no UV until a leaf writes it
+    res.bc = f3(0, 0, 0);
+    res.u = res.v = 0;
+    res.has_bc = res.has_uv = 0;
+    for (int guard = 0; guard < SDF_MAX_MD_STEPS; ++guard) {
         const jsrt_rec_sdfnode &N = S.sdf_nodes[n];
         bool leaf = false;
         switch (N.kind) {
@@ -975,7 +980,7 @@ __device__ __forceinline__ SdfMD sdf_material(const DScene &S, int root, F3 p, c
             const double m = h * h * h * 0.5;
             double mixf = (x < y) ? m : (1.0 - m);
             if (N.kind == JSRT_SDF_SMOOTH_INTERSECTION) mixf = 1.0 - mixf;
-            if (sp >= 8) return res;
+            if (sp >= SDF_MAX_BLEND) return res;
             stk[sp].node = n;
             stk[sp].mixf = mixf;
             stk[sp].stage = 0;

@@ -672,8 +672,24 @@ struct Writer {
         r.max_trace = V.num(g, "max_trace_distance");
         r.normal_step = V.num(g, "normal_step_size");
         const uint32_t box = V.need(g, "aabb");
-        put(r.center, V.vec(V.need(box, "center"), "SDF aabb"));
-        put(r.half, V.vec(V.need(box, "half_size"), "SDF aabb", NULL_INF));
+        // An unbounded box (a Repetition's) under a Matrix: every transformed corner is NaN (0 * inf), so
+        // AABB.fromPoints keeps min = +inf, max = -inf and fromMinMax (geometry.js:94-105) makes the centre
+        // inf + -inf = NaN and the half size (-inf - inf) / 2 = -inf, both written as null.  Every AABB the reference
+        // builds goes through fromMinMax with min / max picked by comparisons (fromPoints, hull, intersection:
+        // geometry.js:106-151), which never pick a NaN, so (+inf, -inf) is the only pair that gives a NaN centre
+        // (hull and getBoundingBox of such a box give it again; expand leaves -inf): on an axis whose centre is
+        // null the half size is -Infinity; elsewhere a null half size is +Infinity.  The NaN is written with the
+        // bits the exporter stored for it (quiet, sign set: 0xFFC00000), whatever this host's default NaN is.
+        std::vector<float> c = V.vec(V.need(box, "center"), "SDF aabb", NULL_NAN);
+        std::vector<float> h = V.vec(V.need(box, "half_size"), "SDF aabb", NULL_INF);
+        const uint32_t nan_bits = 0xFFC00000u;
+        for (size_t i = 0; i < c.size(); ++i)
+            if (c[i] != c[i]) {
+                memcpy(&c[i], &nan_bits, 4);
+                if (i < h.size() && h[i] == INFINITY) h[i] = -INFINITY;
+            }
+        put(r.center, c);
+        put(r.half, h);
         const int32_t idx = push(sdfg, r);
         m_sdfgeom[g] = idx;
         return idx;

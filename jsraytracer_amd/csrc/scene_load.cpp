@@ -596,8 +596,68 @@ struct Loader {
             md = d > md ? d : md; mp = p > mp ? p : mp; ms = sc > ms ? sc : ms; ml = l > ml ? l : ml;
             if (d < 0 || p < 0 || sc < 0 || l < 0) fail("SDF program stack underflow");
         }
-        if (md > SDF_MAX_D || mp > SDF_MAX_P || ms > SDF_MAX_S || ml > SDF_MAX_LOOP)
-            fail("SDF tree too deep/wide for the GPU program stacks");
+        // the message names every stack that overflowed (the tests one past a limit match on it)
+        std::string over;
+        auto note = [&](const char *what, int need, int have) {
+            if (need > have) over += std::string(over.empty() ? ": " : ", ") + what + " " + std::to_string(need) + " > " + std::to_string(have);
+        };
+        note("distance stack", md, SDF_MAX_D);
+        note("point stack", mp, SDF_MAX_P);
+        note("scale stack", ms, SDF_MAX_S);
+        note("loop nesting", ml, SDF_MAX_LOOP);
+        if (!over.empty()) fail("SDF tree too deep/wide for the GPU program stacks" + over);
+    }
+
+    // getMaterialData's walk of the tree under node n (device_common.h sdf_material): the most smooth combinators
+    // whose blend is pending at once (each holds a slot until both its subtrees are done) and the most nodes one
+    // walk visits (a selector follows one child, a smooth combinator both).  Memoised: subtrees may be shared.
+    std::unordered_map<int32_t, std::pair<int32_t, int64_t>> sdf_md_cost;
+    std::pair<int32_t, int64_t> sdf_material_cost(int32_t n) {
+        auto it = sdf_md_cost.find(n);
+        if (it != sdf_md_cost.end()) return it->second;
+        const jsrt_rec_sdfnode &N = sdfnode(n);
+        int32_t blend = 0;
+        int64_t steps = 1;
+        auto take = [&](std::pair<int32_t, int64_t> c) {
+            blend = std::max(blend, c.first);
+            return c.second;
+        };
+        switch (N.kind) {
+        case JSRT_SDF_UNION:
+        case JSRT_SDF_INTERSECTION: {
+            int64_t m = 0;
+            for (int32_t i = 0; i < N.count; ++i) m = std::max(m, take(sdf_material_cost(B.chld[N.first + i])));
+            steps += m;
+            break;
+        }
+        case JSRT_SDF_DIFFERENCE: {
+            const int64_t a = take(sdf_material_cost(N.a)), b = take(sdf_material_cost(N.b));
+            steps += std::max(a, b);
+            break;
+        }
+        case JSRT_SDF_ROUND:
+        case JSRT_SDF_TRANSFORM:
+        case JSRT_SDF_RECURSIVE_UNION: steps += take(sdf_material_cost(N.a)); break;
+        case JSRT_SDF_SMOOTH_UNION:
+        case JSRT_SDF_SMOOTH_INTERSECTION:
+        case JSRT_SDF_SMOOTH_DIFFERENCE: {
+            const int64_t a = take(sdf_material_cost(N.a)), b = take(sdf_material_cost(N.b));
+            steps += a + b;
+            blend += 1;
+            break;
+        }
+        default: break;
+        }
+        return sdf_md_cost[n] = {blend, steps};
+    }
+    void check_sdf_material(int32_t root) {
+        const auto c = sdf_material_cost(root);
+        if (c.first > SDF_MAX_BLEND)
+            fail("SDF smooth combinators nested " + std::to_string(c.first) + " deep: the GPU blend stack holds " +
+                 std::to_string(SDF_MAX_BLEND));
+        if (c.second > SDF_MAX_MD_STEPS)
+            fail("SDF getMaterialData would visit " + std::to_string(c.second) + " nodes: the GPU walk stops at " +
+                 std::to_string(SDF_MAX_MD_STEPS));
     }
 
     // A union of n boxes at sdf_const[a] (4 doubles apart) that is the Menger sponge's cross (device_common.h
@@ -774,6 +834,7 @@ struct Loader {
         compile_sdf(G.root, 0);
         emit(SOP_END);
         check_sdf_stacks(first, S.sdf_insn.size());
+        check_sdf_material(G.root);
         int32_t idx = (int32_t)S.sdfg.size();
         S.sdfg.push_back(G);
         sdfg_of_blob[g] = idx;
@@ -1152,7 +1213,9 @@ struct Loader {
         S.sdf_all_forms = S.sdfg.empty() ? 0 : 1;
         for (const jsrt_rec_sdfgeom &G : S.sdfg) {
             const int32_t pc = S.sdf_range[2 * (size_t)G.root];
-            if (pc < 0 || S.sdf_insn[pc].op != SOP_FORM) S.sdf_all_forms = 0;
+            const int32_t form = (pc >= 0 && S.sdf_insn[pc].op == SOP_FORM) ? S.sdf_insn[pc].a : 0;
+            S.sdf_root_form.push_back(form);
+            if (!form) S.sdf_all_forms = 0;
         }
         shadow_grid();
     }

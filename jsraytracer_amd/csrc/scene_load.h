@@ -43,6 +43,7 @@ struct HostScene {
     std::vector<int32_t> sdf_child;
     std::vector<jsrt_rec_sdfnode> sdf_nodes;
     std::vector<jsrt_rec_sdfgeom> sdfg;
+    std::vector<int32_t> sdf_root_form;  // per sdfg: its root program's SFORM_* id, 0 = the program VM runs it
     DCamera cam;
     float bg[4];
     int32_t kind, spp, max_depth, width, height;

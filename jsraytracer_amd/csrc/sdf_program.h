@@ -65,5 +65,10 @@ constexpr int SDF_MAX_D = 6;    // distance stack depth
 constexpr int SDF_MAX_P = 2;    // point stack depth
 constexpr int SDF_MAX_S = 4;    // scale stack depth
 constexpr int SDF_MAX_LOOP = 2; // nested loops
+// getMaterialData's walk (device_common.h sdf_material): smooth combinators whose blend is pending at once, and
+// the nodes one walk may visit.  The host refuses a tree beyond either (scene_load.cpp check_sdf_material), so
+// the device never meets one.
+constexpr int SDF_MAX_BLEND = 8;
+constexpr int SDF_MAX_MD_STEPS = 256;
 
 }  // namespace jsrt

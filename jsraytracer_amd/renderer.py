@@ -100,6 +100,11 @@ class Scene:
               "jsrt_sdf_distance")
         return out
 
+    def sdf_forms(self):
+        """What the loader decided for this scene's SDFGeometry primitives (include/jsrt.h jsrt_scene_sdf_forms):
+        {"all_forms": 0 / 1, "roots": {OBJS index: form id of its root's program, 0 = the program VM}}."""
+        return _sdf_forms(lambda *a: _native.lib().jsrt_scene_sdf_forms(self._h, *a), "jsrt_scene_sdf_forms")
+
     def material_color(self, mcolor, uv):
         """MaterialColor.color({UV}) of MCOL record `mcolor` (a solid, scaled, checkerboard or texture chain) at
         uv (n x 2 f32) on the device (include/jsrt.h jsrt_material_color): n x 3 f32, r g b."""
@@ -223,6 +228,23 @@ def finish_accum(d_accum_ptr, n, kind, passes, d_rgba_ptr, d_colors_ptr=None, st
 
 def owned_columns(width, x_offset, x_delt, col_block=1):
     return int(_native.lib().jsrt_owned_columns(width, x_offset, x_delt, col_block))
+
+
+def _sdf_forms(call, what):
+    allf, count = ctypes.c_int32(), ctypes.c_size_t()
+    check(call(ctypes.byref(allf), None, None, 0, ctypes.byref(count)), what)
+    n = count.value
+    objs, forms = (ctypes.c_int32 * max(n, 1))(), (ctypes.c_int32 * max(n, 1))()
+    check(call(ctypes.byref(allf), objs, forms, n, ctypes.byref(count)), what)
+    return {"all_forms": int(allf.value), "roots": {int(objs[i]): int(forms[i]) for i in range(n)}}
+
+
+def sdf_forms(blob):
+    """Scene.sdf_forms of a blob without a GPU (include/jsrt.h jsrt_sdf_forms): the loader runs on the host, and
+    raises JsrtError for a scene it refuses, as Scene(blob) would."""
+    blob = bytes(blob)
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    return _sdf_forms(lambda *a: _native.lib().jsrt_sdf_forms(buf, len(blob), *a), "jsrt_sdf_forms")
 
 
 def scene_header(blob):

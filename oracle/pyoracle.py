@@ -115,20 +115,31 @@ def scene_header(blob):
 
 
 # ---- golden fixtures (generated from the reference by oracle/refharness/regen_goldens.sh) ----
-def golden_index():
-    with open(os.path.join(GOLDEN, "index.json")) as f:
+# `sub`: a fixture tree of the same layout below tests/golden ("sdfzoo": oracle/refharness/regen_zoo.sh)
+def _golden(sub, *parts):
+    return os.path.join(GOLDEN, sub, *parts) if sub else os.path.join(GOLDEN, *parts)
+
+
+def golden_index(sub=None):
+    with open(_golden(sub, "index.json")) as f:
         return json.load(f)["renders"]
 
 
-def golden_scene(name):
-    with gzip.open(os.path.join(GOLDEN, "scenes", name + ".jsrt.gz"), "rb") as f:
+def golden_scene(name, sub=None):
+    with gzip.open(_golden(sub, "scenes", name + ".jsrt.gz"), "rb") as f:
         return f.read()
 
 
-def golden_image(tag, width, height):
-    rgba = np.fromfile(os.path.join(GOLDEN, "images", tag + ".rgba"), np.uint8).reshape(height, width, 4)
-    colors = np.fromfile(os.path.join(GOLDEN, "images", tag + ".f32"), np.float32).reshape(height, width, 4)
+def golden_image(tag, width, height, sub=None):
+    rgba = np.fromfile(_golden(sub, "images", tag + ".rgba"), np.uint8).reshape(height, width, 4)
+    colors = np.fromfile(_golden(sub, "images", tag + ".f32"), np.float32).reshape(height, width, 4)
     return colors, rgba
+
+
+def golden_json(name, sub=None):
+    """The reference's Serializer JSON of a scene (oracle/refharness/make_json_fixtures.js), as bytes."""
+    with gzip.open(_golden(sub, "json", name + ".json.gz"), "rb") as f:
+        return f.read()
 
 
 def golden_kats():
@@ -176,12 +187,12 @@ def sdf_distance(blob, obj, points):
     return out
 
 
-def golden_material(name):
+def golden_material(name, sub=None):
     """Known answers computed by the reference (oracle/refharness/make_material_kats.js): the material_data
     of hits ("material": rays, t, obj, normal, position, uv, bary, basecolor) and SDF.distance samples
     ("sdf": [{obj, points, distance}])."""
     import base64
-    with gzip.open(os.path.join(GOLDEN, "material", name + ".json.gz"), "rt") as f:
+    with gzip.open(_golden(sub, "material", name + ".json.gz"), "rt") as f:
         d = json.load(f)
     m = d["material"]
     shapes = {"rays": (np.float32, 6), "t": (np.float64, 0), "obj": (np.int32, 0), "normal": (np.float32, 4),
@@ -195,15 +206,15 @@ def golden_material(name):
     return d
 
 
-def golden_material_scenes():
-    return sorted(f[:-len(".json.gz")] for f in os.listdir(os.path.join(GOLDEN, "material")) if f.endswith(".json.gz"))
+def golden_material_scenes(sub=None):
+    return sorted(f[:-len(".json.gz")] for f in os.listdir(_golden(sub, "material")) if f.endswith(".json.gz"))
 
 
-def golden_casts(name):
+def golden_casts(name, sub=None):
     """World.cast known answers computed by the reference (oracle/refharness/make_cast_kats.js):
     {"blob_sha256", "sets": [{name, minD, maxD, transp, rays (n x 6 f32), t (f64), obj (i32)}]}."""
     import base64
-    with gzip.open(os.path.join(GOLDEN, "casts", name + ".json.gz"), "rt") as f:
+    with gzip.open(_golden(sub, "casts", name + ".json.gz"), "rt") as f:
         d = json.load(f)
     for s in d["sets"]:
         s["maxD"] = float(s["maxD"])
@@ -213,8 +224,8 @@ def golden_casts(name):
     return d
 
 
-def golden_cast_scenes():
-    return sorted(f[:-len(".json.gz")] for f in os.listdir(os.path.join(GOLDEN, "casts")) if f.endswith(".json.gz"))
+def golden_cast_scenes(sub=None):
+    return sorted(f[:-len(".json.gz")] for f in os.listdir(_golden(sub, "casts")) if f.endswith(".json.gz"))
 
 
 # ---- mesh fixtures (oracle/refharness/regen_mesh_fixtures.sh): skeleton + OBJ + MTL per scene ----

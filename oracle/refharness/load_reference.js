@@ -36,8 +36,16 @@ function loadReference() {
 
 // Resolve a test scene: returns a Promise of the {renderer, width, height} the test's
 // configureTest(callback) produces (tests/<name>/test.mjs).
+// A name one of this project's own scene modules defines (LOCAL_SCENES: modules beside this file exporting
+// `scenes`, name -> function returning that same object) resolves there instead.
+const LOCAL_SCENES = ["./zoo_scenes"];
+
 function loadScene(name) {
     loadReference();
+    for (const mod of LOCAL_SCENES) {
+        const local = require(mod).scenes;
+        if (Object.prototype.hasOwnProperty.call(local, name)) return Promise.resolve().then(() => local[name]());
+    }
     const testsDir = path.join(REF, "tests");
     process.chdir(testsDir); // objloader paths are relative ("../assets/...")
     return import(path.join(testsDir, name, "test.mjs")).then(m => new Promise((resolve, reject) => {

@@ -13,7 +13,8 @@
  *   "shadow"   -- segments p -> q between such points, World.cast(ray, 0.0001, 1, false) as
  *                 materials.js:250-252 casts them (shadow-casting objects only).
  *
- *   node oracle/refharness/make_cast_kats.js <outdir> <scene>...
+ *   node oracle/refharness/make_cast_kats.js [--primary=WxH] [--random=N] [--shadow=N] <outdir> <scene>...
+ * (--primary: the pixel centres of a W x H image instead of the 16 x 16 grid; defaults 16x16, 512, 256)
  * writes <outdir>/<scene>.json: {scene, blob_sha256, sets: [{name, minD, maxD, transp, n,
  *   rays: base64 f32 n x 6 (origin xyz w=1, direction xyz w=0), t: base64 f64 n, obj: base64 i32 n}]}
  */
@@ -28,10 +29,17 @@ function r() { s = (Math.imul(s, 1103515245) + 12345) >>> 0; return s / 42949672
 const b64 = (typed) => Buffer.from(typed.buffer, typed.byteOffset, typed.byteLength).toString("base64");
 
 async function main() {
-    const outdir = path.resolve(process.argv[2]);
+    const argv = process.argv.slice(2), opt = { primary: "16x16", random: "512", shadow: "256" };
+    while (argv.length && argv[0].startsWith("--")) {
+        const [k, v] = argv.shift().slice(2).split("=");
+        if (!(k in opt) || !v) throw new Error("unknown option --" + k);
+        opt[k] = v;
+    }
+    const [PW, PH] = opt.primary.split("x").map(Number), NRND = Number(opt.random), NSH = Number(opt.shadow);
+    const outdir = path.resolve(argv[0]);
     fs.mkdirSync(outdir, { recursive: true });
     const Vec = refClass("Vec"), Ray = refClass("Ray");
-    for (const name of process.argv.slice(3)) {
+    for (const name of argv.slice(1)) {
         const test = await loadScene(name);
         const w = new SceneBlobWriter();
         const blob = w.build(test);
@@ -57,17 +65,17 @@ async function main() {
         const isDof = cam.constructor.name === "DepthOfFieldPerspectiveCamera";
         if (!isDof) {
             const rays = [];
-            for (let j = 0; j < 16; ++j)
-                for (let i = 0; i < 16; ++i) rays.push(cam.getRayForPixel(2 * (i + 0.5) / 16 - 1, 1 - 2 * (j + 0.5) / 16));
+            for (let j = 0; j < PH; ++j)
+                for (let i = 0; i < PW; ++i) rays.push(cam.getRayForPixel(2 * (i + 0.5) / PW - 1, 1 - 2 * (j + 0.5) / PH));
             run("primary", rays, 0, Infinity, true);
         }
         const rnd = [], sh = [];
-        for (let k = 0; k < 512; ++k) {
+        for (let k = 0; k < NRND; ++k) {
             const th = 2 * Math.PI * r(), z = 2 * r() - 1, q = Math.sqrt(1 - z * z);
             rnd.push(new Ray(point(), Vec.of(q * Math.cos(th), q * Math.sin(th), z, 0)));
         }
         run("random", rnd, 0, Infinity, true);
-        for (let k = 0; k < 256; ++k) {
+        for (let k = 0; k < NSH; ++k) {
             const p = point(), q = point();
             sh.push(new Ray(p, q.minus(p)));
         }

@@ -92,7 +92,12 @@ async function main() {
             });
         }
         const sdf = [];
-        for (const o of world.objects) {
+        // the world's own objects first (so their points keep their place in the r() stream), then the objects
+        // inside its Aggregates, depth first
+        const prims = world.objects.slice();
+        const walk = (o) => { if (Array.isArray(o.objects)) o.objects.forEach(c => { prims.push(c); walk(c); }); };
+        world.objects.forEach(walk);
+        for (const o of prims) {
             if (!o.geometry || o.geometry.constructor.name !== "SDFGeometry") continue;
             const root = o.geometry.root_sdf;
             const bb = root.getBoundingBox(refClass("Mat4").identity(), refClass("Mat4").identity());

@@ -7,7 +7,9 @@ oracle/refharness/make_material_kats.js), through the C ABI (jsrt_material_data,
     texture coordinate, is not compared);
   * SDF.distance (sdf.js:53-477) of every SDFGeometry primitive at random points and hit points, bit for
     bit: the same program VM the render's sphere tracing runs.
-A render that differs can then be narrowed to one hit's shading input."""
+A render that differs can then be narrowed to one hit's shading input.
+(The 28 scenes are tests/golden's; their seven SDF scenes are all recognised program forms.  The SDF trees that run
+the program VM, and the load-time SDF knobs, are in tests/test_gpu_sdfzoo.py.)"""
 import numpy as np
 import pytest
 
