@@ -16,6 +16,8 @@
  *                          and the hit Primitive (known-answer tests localise parity to one cast)
  *   jsrt_material_data  <- World.color(ray, 1) up to Material.color (world.js:31-41, 125-137):
  *                          Geometry.materialData + the world normal / position of each hit
+ *   jsrt_material_uv    <- the data.UV a base material's color() receives, after any PositionalUVMaterial
+ *                          (src/materials.js:177-193) above it rewrote it from the hit position
  *   jsrt_sdf_distance   <- SDF.distance (src/sdf.js:53-74) of an SDFGeometry primitive's root
  *   jsrt_material_color <- MaterialColor.color({UV}) (src/materials.js:20-131) of one colour chain: solid,
  *                          scaled, checkerboard or texture (TextureMaterialColor.color, :101-130)
@@ -185,6 +187,14 @@ int jsrt_scene_sdf_forms(jsrt_scene *scene, int32_t *all_forms, int32_t *objects
  * solid, scaled, checkerboard or texture chain -- at n UV pairs (n x 2 f32): out_rgb n x 3 f32, the colour's
  * first three components (a texture's alpha is not produced).  Synchronous. */
 int jsrt_material_color(jsrt_scene *scene, int32_t mcolor_index, const float *uv, size_t n, float *out_rgb);
+
+/* The UV pair the base material's colour chains read at the closest hit of each of n rays (as jsrt_cast): the
+ * geometry's UV (geometry.js materialData), or, under a PositionalUVMaterial (materials.js:177-193), the mapping of
+ * the world hit point by the innermost wrapper -- data.UV as Phong / Fresnel / PathTracing / SolidColor /
+ * Transparent .color receives it.  out_uv n x 2 f32, out_has_uv n x i32: 0 on a miss and where the reference's
+ * data.UV is undefined (the pair is NaN there).  It runs shade_node's own surface_data and mapping function.
+ * Synchronous. */
+int jsrt_material_uv(jsrt_scene *scene, const float *rays, size_t n, float *out_uv, int32_t *out_has_uv);
 
 /* Number of owned columns for (W, x_offset, x_delt, col_block). */
 int32_t jsrt_owned_columns(int32_t width, int32_t x_offset, int32_t x_delt, int32_t col_block);

@@ -63,6 +63,25 @@ int jsrt_blob_attach_obj(const void *blob, size_t n, const char *obj_text, size_
 int jsrt_blob_attach_obj_mtl(const void *blob, size_t n, const char *obj_text, size_t obj_len, const char *mtl_text,
                              size_t mtl_len, const jsrt_mesh_options *options, void **out_blob, size_t *out_n,
                              jsrt_mesh_info *info);
+
+/* jsrt_blob_attach_obj_mtl with the MTL texture maps (parseMtlFile / makeMaterial, objloader.js:9-20, 58-116):
+ * `map_Ka` / `map_Kd` / `map_Ks NAME` (NAME = the line's last token) take the image of that name from `textures`,
+ * already decoded to RGBA8 (row-major, top row first; the reference decodes through createImageBitmap, this library
+ * ships no decoder).  Each name becomes one TextureMaterialColor shared by every material naming it (bilinear,
+ * clampU = clampV = true: TextureMaterialColor.fromBitmap); a map with a K* colour is ScaledMaterialColor(texture,
+ * K*), a map alone the texture.  A name that is not supplied throws "Unknown texture: NAME" (a name parseFloat reads
+ * as a number is looked up as that number's string, as the reference does); map_Ns stays "Unsupported material
+ * parameter: map_Ns".  The result is laid out as jsraytracer_amd/js/scene_blob.js writes the same live scene: records
+ * in the exporter's walk order, unreferenced ones (the template primitive and its tree) dropped.  Scenes with SDF
+ * geometry are refused by this entry point. */
+typedef struct {
+    const char *name;      /* NUL-terminated file name as the MTL writes it */
+    const uint8_t *rgba8;  /* width * height * 4 bytes */
+    uint32_t width, height;
+} jsrt_mesh_texture;
+int jsrt_blob_attach_obj_mtl_tex(const void *blob, size_t n, const char *obj_text, size_t obj_len, const char *mtl_text,
+                                 size_t mtl_len, const jsrt_mesh_texture *textures, size_t n_textures,
+                                 const jsrt_mesh_options *options, void **out_blob, size_t *out_n, jsrt_mesh_info *info);
 void jsrt_blob_free(void *blob);
 
 #ifdef __cplusplus

@@ -49,6 +49,9 @@
  * sections are absent from a scene without textures. */
 #define JSRT_SEC_TEXTURE JSRT_FOURCC('T', 'E', 'X', 'R')
 #define JSRT_SEC_TEXEL JSRT_FOURCC('T', 'E', 'X', 'L')
+/* position-to-UV mappings (materials.js:177-193 PositionalUVMaterial): one record per wrapper material.  Absent from
+ * a scene without the class. */
+#define JSRT_SEC_POSUV JSRT_FOURCC('P', 'U', 'V', 'M')
 
 /* renderer kinds: renderers.js:1 SimpleRenderer, :65 IncrementalMultisamplingRenderer,
  * :47 RandomMultisamplingRenderer */
@@ -67,13 +70,15 @@ enum {
 /* texture modes: materials.js:109 "bilinear", :114 "nearest" */
 enum { JSRT_TEX_BILINEAR = 0, JSRT_TEX_NEAREST = 1 };
 /* materials: materials.js:195 Phong, :294 FresnelPhong, :389 PhongPathTracing, :145 SolidColor,
- * :160 Transparent */
+ * :160 Transparent, :177 PositionalUV (a wrapper: base = MATL idx of baseMaterial, color = PUVM idx, every other
+ * index -1 and every double 0) */
 enum {
     JSRT_MAT_PHONG = 1,
     JSRT_MAT_FRESNEL = 2,
     JSRT_MAT_PATH = 3,
     JSRT_MAT_SOLID = 4,
-    JSRT_MAT_TRANSPARENT = 5
+    JSRT_MAT_TRANSPARENT = 5,
+    JSRT_MAT_POSITIONAL_UV = 6
 };
 /* geometry: geometry.js:239 SimplePlane (and :257 Plane), :280 Square, :303 Circle, :412 Sphere,
  * :458 Cylinder, :77 AABB (:230 UnitBox), :334 Triangle, sdf.js:1 SDFGeometry */
@@ -222,6 +227,12 @@ typedef struct { /* TEXR (materials.js:78-87): _imgdata.width / height, mode, cl
 } jsrt_rec_texture;
 /* TEXL: raw bytes (count = bytes) */
 
+typedef struct { /* PUVM (materials.js:178-184): origin, u_axis, v_axis and their Vec lengths (3 or 4; an axis no
+                    longer than origin); components past a length are 0 */
+    float origin[4], u_axis[4], v_axis[4];
+    uint32_t origin_len, u_len, v_len, pad;
+} jsrt_rec_posuv;
+
 #ifdef __cplusplus
 #define JSRT_STATIC_ASSERT static_assert
 #else
@@ -242,5 +253,6 @@ JSRT_STATIC_ASSERT(sizeof(jsrt_rec_light) == 304, "light");
 JSRT_STATIC_ASSERT(sizeof(jsrt_rec_sdfnode) == 336, "sdfnode");
 JSRT_STATIC_ASSERT(sizeof(jsrt_rec_sdfgeom) == 64, "sdfgeom");
 JSRT_STATIC_ASSERT(sizeof(jsrt_rec_texture) == 32, "texture");
+JSRT_STATIC_ASSERT(sizeof(jsrt_rec_posuv) == 64, "posuv");
 
 #endif

@@ -51,11 +51,12 @@ RC_ABORTED = -4  # jsrt_render_device_progress_ex: the callback asked to stop th
 
 # exported symbols of include/jsrt.h (checked by tests/test_capi_symbols.py)
 EXPORTS = ["jsrt_scene_create", "jsrt_scene_destroy", "jsrt_render", "jsrt_render_device", "jsrt_cast",
-           "jsrt_material_data", "jsrt_sdf_distance", "jsrt_material_color", "jsrt_owned_columns", "jsrt_last_error", "jsrt_abi_version",
+           "jsrt_material_data", "jsrt_material_uv", "jsrt_sdf_distance", "jsrt_material_color", "jsrt_owned_columns", "jsrt_last_error", "jsrt_abi_version",
            "jsrt_device_count", "jsrt_build_id", "jsrt_render_device_progress", "jsrt_render_device_progress_ex",
            "jsrt_render_device_accum", "jsrt_finish_accum", "jsrt_sdf_forms", "jsrt_scene_sdf_forms"]
 # exported symbols of include/jsrt_mesh.h (native OBJ ingest + BVH build; host-only, no GPU needed)
-MESH_EXPORTS = ["jsrt_blob_attach_obj", "jsrt_blob_attach_obj_mtl", "jsrt_blob_free"]
+MESH_EXPORTS = ["jsrt_blob_attach_obj", "jsrt_blob_attach_obj_mtl", "jsrt_blob_attach_obj_mtl_tex", "jsrt_blob_free"]
+
 # exported symbols of include/jsrt_json.h (Serializer-JSON reader; host-only)
 JSON_EXPORTS = ["jsrt_blob_from_json"]
 # exported symbols of include/jsrt_texture.h (an MCOL record turned into a texture; host-only)
@@ -64,6 +65,10 @@ TEXTURE_EXPORTS = ["jsrt_blob_set_texture"]
 
 class MeshOptions(ctypes.Structure):
     _fields_ = [("bvh_object", ctypes.c_int32), ("pad", ctypes.c_int32), ("min_area", ctypes.c_double)]
+
+
+class MeshTexture(ctypes.Structure):  # jsrt_mesh_texture
+    _fields_ = [("name", ctypes.c_char_p), ("rgba8", ctypes.c_void_p), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32)]
 
 
 class JsonInfo(ctypes.Structure):
@@ -180,6 +185,30 @@ def texture_api():
     L.jsrt_blob_set_texture.restype = ctypes.c_int
     L.jsrt_blob_set_texture.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int32, ctypes.c_void_p] + \
         [ctypes.c_int32] * 5 + [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+    return L
+
+
+def posuv_api():
+    """The library with jsrt_material_uv bound (JsrtError if it lacks it): bound where it is called, as the texture
+    entry points are, so an A/B library built from a tree that predates it still loads and renders."""
+    L = lib()
+    if not hasattr(L, "jsrt_material_uv"):
+        raise JsrtError(f"{LIB_PATH} has no jsrt_material_uv: rebuild it")
+    L.jsrt_material_uv.restype = ctypes.c_int
+    L.jsrt_material_uv.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    return L
+
+
+def mesh_texture_api():
+    """The library with jsrt_blob_attach_obj_mtl_tex bound (JsrtError if it lacks it); bound where it is called."""
+    L = lib()
+    if not hasattr(L, "jsrt_blob_attach_obj_mtl_tex"):
+        raise JsrtError(f"{LIB_PATH} has no jsrt_blob_attach_obj_mtl_tex: rebuild it")
+    L.jsrt_blob_attach_obj_mtl_tex.restype = ctypes.c_int
+    L.jsrt_blob_attach_obj_mtl_tex.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
+                                               ctypes.c_size_t, ctypes.POINTER(MeshTexture), ctypes.c_size_t,
+                                               ctypes.POINTER(MeshOptions), ctypes.POINTER(ctypes.c_void_p),
+                                               ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(MeshInfo)]
     return L
 
 

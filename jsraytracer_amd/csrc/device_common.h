@@ -1754,6 +1754,7 @@ __device__ __forceinline__ void persistent_cast(const DScene &S, uint32_t *ctr, 
 // materials (materials.js)
 }  // namespace jsrt
 #include "texture_sample.h"
+#include "posuv_map.h"
 namespace jsrt {
 // TEX: the chain may end in a texture (DScene::has_textures; k_shade's and k_material_color's instantiations).
 // Without it no sampler code is emitted, and a scene with textures never runs such an instantiation on a chain

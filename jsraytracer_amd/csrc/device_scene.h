@@ -114,8 +114,9 @@ struct DCamera {         // cameras.js:18-53
 
 // material flags: MATF_UV colours depend on (u, v) (a checkerboard or a texture in some chain); MATF_DIFF_CONST /
 // MATF_SPEC_CONST the diffuse / specular chain is a constant (mc_const); MATF_SPEC_ZERO the specular colour
-// is the constant (+0, +0, +0) and the smoothness in [0, 1e5] (render_levels.h: no specular power)
-enum { MATF_UV = 1, MATF_DIFF_CONST = 2, MATF_SPEC_CONST = 4, MATF_SPEC_ZERO = 8 };
+// is the constant (+0, +0, +0) and the smoothness in [0, 1e5] (render_levels.h: no specular power); MATF_PUV a
+// flattened PositionalUVMaterial chain: (u, v) come from DScene::puv of the hit point, not from the geometry
+enum { MATF_UV = 1, MATF_DIFF_CONST = 2, MATF_SPEC_CONST = 4, MATF_SPEC_ZERO = 8, MATF_PUV = 16 };
 
 struct DScene {
     const DPrim *prims;
@@ -179,12 +180,16 @@ struct DScene {
     const jsrt_rec_texture *tex;
     const uint8_t *texels;
     const double *tex_q255;
-    int32_t has_textures, pad_tex;
+    // has_posuv: some material is a flattened PositionalUVMaterial (materials.js:177-193; posuv_map.h), so k_shade
+    // runs its PUV instantiation; puv: per material its mapping (read for MATF_PUV materials only).
+    int32_t has_textures, has_posuv;
+    const jsrt_rec_posuv *puv;
 };
 enum {  // DScene::stab tables, in image order: k_shadow's first (mat .. sample_light), then k_shade's
     STAB_MAT, STAB_MAT_FLAGS, STAB_MC, STAB_MC_CONST, STAB_SAMPLE_CALL, STAB_SAMPLE_LIGHT,
-    STAB_PRIMS, STAB_PRIM_SHADE, STAB_SHADE0, STAB_SHADEI, STAB_PRIM_LIT, STAB_N
+    STAB_PRIMS, STAB_PRIM_SHADE, STAB_SHADE0, STAB_SHADEI, STAB_PRIM_LIT, STAB_POSUV, STAB_N
 };
+static_assert(STAB_N <= 12, "DScene::stab_off");
 constexpr int STAB_MAX_WORDS = 1024;  // 16 KB of LDS at most
 
 // Dynamic LDS of a casting kernel over a scene with BVHs: per lane a traversal stack of bvh_stack

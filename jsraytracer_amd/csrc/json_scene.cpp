@@ -472,6 +472,7 @@ struct Writer {
     std::vector<jsrt_rec_light> lite;
     std::vector<jsrt_rec_sdfnode> sdfn;
     std::vector<jsrt_rec_sdfgeom> sdfg;
+    std::vector<jsrt_rec_posuv> puvm;  // (its section is written only when a material is a PositionalUVMaterial)
     std::unordered_map<uint32_t, int32_t> m_mc, m_mat, m_geom, m_obj, m_bvh, m_sdf, m_sdfgeom;
     std::unordered_map<uint64_t, int32_t> m_matrix;   // (m node, inv node)
     std::unordered_map<std::string, int32_t> m_matrix_bytes;
@@ -564,6 +565,25 @@ struct Writer {
         auto it = m_mat.find(m);
         if (it != m_mat.end()) return it->second;
         jsrt_rec_material r = zero<jsrt_rec_material>();
+        if (V.isA(m, "PositionalUVMaterial")) {  // fields as written (materials.js:178-184), as scene_blob.js matIndex
+            r.kind = JSRT_MAT_POSITIONAL_UV;
+            r.base = r.ambient = r.diffuse = r.specular = r.reflect = r.transmit = r.color = -1;
+            r.base = mat_index(V.field(m, "baseMaterial"));
+            const auto o = V.vec(V.need(m, "origin"), "PositionalUVMaterial.origin"),
+                       u = V.vec(V.need(m, "u_axis"), "PositionalUVMaterial.u_axis"),
+                       v = V.vec(V.need(m, "v_axis"), "PositionalUVMaterial.v_axis");
+            jsrt_rec_posuv p = zero<jsrt_rec_posuv>();
+            put(p.origin, o);
+            put(p.u_axis, u);
+            put(p.v_axis, v);
+            p.origin_len = (uint32_t)o.size();
+            p.u_len = (uint32_t)u.size();
+            p.v_len = (uint32_t)v.size();
+            r.color = push(puvm, p);
+            const int32_t idx = push(matl, r);
+            m_mat[m] = idx;
+            return idx;
+        }
         uint32_t kind;
         if (V.isA(m, "PhongPathTracingMaterial")) kind = JSRT_MAT_PATH;
         else if (V.isA(m, "FresnelPhongMaterial")) kind = JSRT_MAT_FRESNEL;
@@ -913,7 +933,7 @@ struct Writer {
             const void *p;
             size_t count, size;
         };
-        const Sec secs[] = {
+        std::vector<Sec> secs = {
             {JSRT_SEC_RENDERER, rndr.data(), rndr.size(), sizeof(jsrt_rec_renderer)},
             {JSRT_SEC_CAMERA, camr.data(), camr.size(), sizeof(jsrt_rec_camera)},
             {JSRT_SEC_MCOLOR, mcol.data(), mcol.size(), sizeof(jsrt_rec_mcolor)},
@@ -929,7 +949,8 @@ struct Writer {
             {JSRT_SEC_SDFNODE, sdfn.data(), sdfn.size(), sizeof(jsrt_rec_sdfnode)},
             {JSRT_SEC_SDFGEOM, sdfg.data(), sdfg.size(), sizeof(jsrt_rec_sdfgeom)},
         };
-        const size_t ns = sizeof secs / sizeof secs[0];
+        if (!puvm.empty()) secs.push_back({JSRT_SEC_POSUV, puvm.data(), puvm.size(), sizeof(jsrt_rec_posuv)});
+        const size_t ns = secs.size();
         const size_t hdr = sizeof(jsrt_blob_header) + ns * sizeof(jsrt_section);
         size_t off = (hdr + 7) & ~(size_t)7, total = off;
         for (const Sec &s : secs) total += (s.count * s.size + 7) & ~(size_t)7;

@@ -12,10 +12,12 @@
 // Host code only: nothing here touches the GPU.
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include <map>
 #include <string>
@@ -202,7 +204,36 @@ namespace jsrt {
 namespace objp {
 // parseMtlFile (objloader.js:58-123) over the text of every mtllib, in order (loadMtlFiles merges them
 // with Object.assign).
-void parse_mtl(const char *text, size_t n, MtlLib &lib) {
+// Number::toString (ECMA-262 §6.1.6.1.20) of a finite or infinite double: the key `textures[t[last]]` is looked up
+// under once parseFloat turned the token into a number (objloader.js:88-92, 102)
+static std::string js_number_to_string(double x) {
+    if (x != x) return "NaN";
+    if (x == 0) return "0";
+    if (std::isinf(x)) return x < 0 ? "-Infinity" : "Infinity";
+    char buf[40];
+    int prec = 1;
+    for (; prec <= 17; ++prec) {  // the shortest digit string that round-trips
+        snprintf(buf, sizeof buf, "%.*e", prec - 1, x);
+        if (strtod(buf, nullptr) == x) break;
+    }
+    std::string digits;
+    const char *p = buf;
+    const bool neg = *p == '-';
+    if (neg) ++p;
+    for (; *p && *p != 'e'; ++p)
+        if (*p != '.') digits += *p;
+    const int e = atoi(p + 1), k = (int)digits.size(), nn = e + 1;  // value = 0.digits x 10^nn
+    std::string s;
+    if (k <= nn && nn <= 21) s = digits + std::string(nn - k, '0');
+    else if (0 < nn && nn <= 21) s = digits.substr(0, nn) + "." + digits.substr(nn);
+    else if (-6 < nn && nn <= 0) s = "0." + std::string(-nn, '0') + digits;
+    else {
+        s = digits.substr(0, 1) + (k > 1 ? "." + digits.substr(1) : "") + "e" + (nn - 1 < 0 ? "-" : "+") + std::to_string(abs(nn - 1));
+    }
+    return neg ? "-" + s : s;
+}
+
+void parse_mtl(const char *text, size_t n, MtlLib &lib, const std::map<std::string, int32_t> *textures) {
     std::vector<std::string> t;
     const char *p = text, *end = text + n;
     bool have = false;
@@ -249,7 +280,16 @@ void parse_mtl(const char *text, size_t n, MtlLib &lib) {
                 }
             }
         } else if (k == "map_Ka" || k == "map_Kd" || k == "map_Ks") {
-            fail("MTL textures (" + k + ") are browser-only in the reference and not supported");
+            if (!textures) fail("MTL textures (" + k + ") are browser-only in the reference and not supported");
+            // textures[t[t.length - 1]] after `t[i] = num` for every token parseFloat reads as a number
+            std::string key = t.back();
+            if (t.size() > 1) {  // (a bare statement looks up its own name, t[0])
+                const double num = js_parse_float(key);
+                if (num == num) key = js_number_to_string(num);
+            }
+            auto it = textures->find(key);
+            if (it == textures->end()) fail("Unknown texture: " + key);
+            (k == "map_Ka" ? cur.map_ka : k == "map_Kd" ? cur.map_kd : cur.map_ks) = it->second;
         } else {
             fail("Unsupported material parameter: " + k);
         }
@@ -596,7 +636,40 @@ void put4(float *dst, const float *src) { memcpy(dst, src, 16); }
 // PhongMaterial(Vec.of(1,1,1), ambient, diffuse, specular, Ns || 0) with ambient / diffuse / specular
 // = Solid(K? given ? K? : Vec.of(0,0,0)) and reflectivity = transmissivity = Scaled(White, 0)
 // (PhongMaterial defaults, materials.js:196-205).  Encoded as jsraytracer_amd/js/scene_blob.js does.
-int32_t mtl_material(Sections &S, const MtlMat &m, int32_t &white) {
+// The caller's decoded images and the records made from them so far: one TEXR descriptor and one MCOL texture
+// record per file name (loadTextures builds one TextureMaterialColor per name, objloader.js:42-56), created at the
+// first material that names it.
+struct MtlTextures {
+    const jsrt_mesh_texture *tex = nullptr;
+    size_t n = 0;
+    std::vector<int32_t> mc;  // per texture: its MCOL record or -1
+};
+
+int32_t mtl_texture(Sections &S, MtlTextures &T, int32_t i) {
+    if (T.mc[i] >= 0) return T.mc[i];
+    uint32_t cnt;
+    if (S.find(JSRT_SEC_TEXTURE) < 0) (void)recs<uint8_t>(S, JSRT_SEC_TEXTURE, cnt);
+    if (S.find(JSRT_SEC_TEXEL) < 0) (void)recs<uint8_t>(S, JSRT_SEC_TEXEL, cnt);
+    const int tl = S.find(JSRT_SEC_TEXEL);
+    jsrt_rec_texture r;
+    memset(&r, 0, sizeof r);
+    r.width = T.tex[i].width;
+    r.height = T.tex[i].height;
+    r.mode = JSRT_TEX_BILINEAR;  // TextureMaterialColor.fromBitmap: the constructor's defaults
+    r.clamp_u = r.clamp_v = 1;
+    r.offset = S.data[tl].size();
+    const size_t bytes = (size_t)r.width * r.height * 4;
+    S.data[tl].insert(S.data[tl].end(), T.tex[i].rgba8, T.tex[i].rgba8 + bytes);
+    S.counts[tl] = (uint32_t)S.data[tl].size();
+    jsrt_rec_mcolor c;
+    memset(&c, 0, sizeof c);
+    c.kind = JSRT_MC_TEXTURE;
+    c.a = append(S, JSRT_SEC_TEXTURE, r);
+    c.b = -1;
+    return T.mc[i] = append(S, JSRT_SEC_MCOLOR, c);
+}
+
+int32_t mtl_material(Sections &S, const MtlMat &m, int32_t &white, MtlTextures *T = nullptr) {
     auto solid = [&](const float *v) {
         jsrt_rec_mcolor r;
         memset(&r, 0, sizeof r);
@@ -621,9 +694,24 @@ int32_t mtl_material(Sections &S, const MtlMat &m, int32_t &white) {
     memset(&M, 0, sizeof M);
     M.kind = JSRT_MAT_PHONG;
     M.base = solid(one);
-    M.ambient = solid(m.ka ? m.Ka : zero);
-    M.diffuse = solid(m.kd ? m.Kd : zero);
-    M.specular = solid(m.ks ? m.Ks : zero);
+    // makeMaterialColor(map, K) (objloader.js:1-7): a map with a colour is ScaledMaterialColor(texture, K) with a
+    // Vec scale, a map alone the texture, a colour alone (or nothing) a solid colour
+    auto chain = [&](int32_t map, bool has, const float *K) {
+        if (map < 0 || !T) return solid(has ? K : zero);
+        const int32_t t = mtl_texture(S, *T, map);
+        if (!has) return t;
+        jsrt_rec_mcolor r;
+        memset(&r, 0, sizeof r);
+        r.kind = JSRT_MC_SCALED_VEC;
+        r.a = t;
+        r.b = -1;
+        r.len = 3;
+        for (int i = 0; i < 3; ++i) r.vec[i] = K[i];
+        return append(S, JSRT_SEC_MCOLOR, r);
+    };
+    M.ambient = chain(m.map_ka, m.ka, m.Ka);
+    M.diffuse = chain(m.map_kd, m.kd, m.Kd);
+    M.specular = chain(m.map_ks, m.ks, m.Ks);
     M.reflect = scaled0();
     M.transmit = scaled0();
     M.color = -1;
@@ -634,14 +722,202 @@ int32_t mtl_material(Sections &S, const MtlMat &m, int32_t &white) {
     return append(S, JSRT_SEC_MATERIAL, M);
 }
 
+// The blob re-laid as jsraytracer_amd/js/scene_blob.js writes the live scene it describes: every record reached from
+// the world's objects and lights, in the exporter's walk order (objIndex / bvhIndex / geomIndex / matIndex / mcIndex
+// / texIndex, each de-duplicated by identity = its index here, matrices by their bytes), the sections in the
+// exporter's order.  What nothing references -- the template primitive and its one-leaf tree, the template's material
+// and texture when no triangle shares them -- is dropped.
+struct Canon {
+    Sections &I;
+    Sections O;
+    std::map<int32_t, int32_t> obj, bvh, geom, mat, mc, tex;
+    std::map<std::string, int32_t> matrix;
+    template <class R>
+    R in(uint32_t tag, int32_t i, const char *what) {
+        const int s = I.find(tag);
+        if (s < 0 || i < 0 || (uint32_t)i >= I.counts[s] || I.data[s].size() != (size_t)I.counts[s] * sizeof(R))
+            fail(std::string(what) + " index out of range", -1);
+        R r;
+        memcpy(&r, I.data[s].data() + (size_t)i * sizeof(R), sizeof r);
+        return r;
+    }
+    template <class R>
+    void set(uint32_t tag, int32_t i, const R &r) { memcpy(O.data[O.find(tag)].data() + (size_t)i * sizeof(R), &r, sizeof r); }
+
+    explicit Canon(Sections &in_) : I(in_) {
+        uint32_t c;
+        for (uint32_t tag : {JSRT_SEC_RENDERER, JSRT_SEC_CAMERA, JSRT_SEC_MCOLOR, JSRT_SEC_MATERIAL, JSRT_SEC_GEOMETRY,
+                             JSRT_SEC_OBJECT, JSRT_SEC_MATRIX, JSRT_SEC_ROOT, JSRT_SEC_CHILD, JSRT_SEC_BVHNODE,
+                             JSRT_SEC_TRIANGLE, JSRT_SEC_LIGHT, JSRT_SEC_SDFNODE, JSRT_SEC_SDFGEOM})
+            (void)recs<uint8_t>(O, tag, c);
+    }
+    int32_t matrix_index(int32_t i) {
+        const jsrt_rec_matrix r = in<jsrt_rec_matrix>(JSRT_SEC_MATRIX, i, "matrix");
+        std::string key((const char *)&r, sizeof r);
+        auto it = matrix.find(key);
+        if (it != matrix.end()) return it->second;
+        return matrix[key] = append(O, JSRT_SEC_MATRIX, r);
+    }
+    int32_t tex_index(int32_t i) {
+        auto it = tex.find(i);
+        if (it != tex.end()) return it->second;
+        uint32_t c;
+        if (O.find(JSRT_SEC_TEXTURE) < 0) {
+            (void)recs<uint8_t>(O, JSRT_SEC_TEXTURE, c);
+            (void)recs<uint8_t>(O, JSRT_SEC_TEXEL, c);
+        }
+        jsrt_rec_texture r = in<jsrt_rec_texture>(JSRT_SEC_TEXTURE, i, "texture");
+        const int si = I.find(JSRT_SEC_TEXEL), so = O.find(JSRT_SEC_TEXEL);
+        const uint64_t bytes = (uint64_t)r.width * r.height * 4;
+        if (si < 0 || r.offset > I.data[si].size() || bytes > I.data[si].size() - r.offset) fail("texture texels out of range", -1);
+        const uint64_t at = O.data[so].size();
+        O.data[so].insert(O.data[so].end(), I.data[si].begin() + r.offset, I.data[si].begin() + r.offset + bytes);
+        O.counts[so] = (uint32_t)O.data[so].size();
+        r.offset = at;
+        return tex[i] = append(O, JSRT_SEC_TEXTURE, r);
+    }
+    int32_t mc_index(int32_t i, int depth = 0) {
+        if (i < 0) return -1;
+        auto it = mc.find(i);
+        if (it != mc.end()) return it->second;
+        if (depth > 16) fail("material colour nesting too deep", -1);
+        jsrt_rec_mcolor r = in<jsrt_rec_mcolor>(JSRT_SEC_MCOLOR, i, "material colour");
+        if (r.kind == JSRT_MC_SCALED_SCALAR || r.kind == JSRT_MC_SCALED_VEC) r.a = mc_index(r.a, depth + 1);
+        else if (r.kind == JSRT_MC_CHECKER) {
+            r.a = mc_index(r.a, depth + 1);
+            r.b = mc_index(r.b, depth + 1);
+        } else if (r.kind == JSRT_MC_TEXTURE) r.a = tex_index(r.a);
+        return mc[i] = append(O, JSRT_SEC_MCOLOR, r);
+    }
+    int32_t mat_index(int32_t i, int depth = 0) {
+        auto it = mat.find(i);
+        if (it != mat.end()) return it->second;
+        if (depth > 16) fail("material nesting too deep", -1);
+        jsrt_rec_material r = in<jsrt_rec_material>(JSRT_SEC_MATERIAL, i, "material");
+        if (r.kind == JSRT_MAT_POSITIONAL_UV) {
+            uint32_t c;
+            r.base = mat_index(r.base, depth + 1);
+            if (O.find(JSRT_SEC_POSUV) < 0) (void)recs<uint8_t>(O, JSRT_SEC_POSUV, c);
+            r.color = append(O, JSRT_SEC_POSUV, in<jsrt_rec_posuv>(JSRT_SEC_POSUV, r.color, "mapping"));
+        } else if (r.kind == JSRT_MAT_SOLID || r.kind == JSRT_MAT_TRANSPARENT) r.color = mc_index(r.color);
+        else {
+            r.base = mc_index(r.base);
+            r.ambient = mc_index(r.ambient);
+            r.diffuse = mc_index(r.diffuse);
+            r.specular = mc_index(r.specular);
+            r.reflect = mc_index(r.reflect);
+            r.transmit = mc_index(r.transmit);
+        }
+        return mat[i] = append(O, JSRT_SEC_MATERIAL, r);
+    }
+    int32_t geom_index(int32_t i) {
+        auto it = geom.find(i);
+        if (it != geom.end()) return it->second;
+        jsrt_rec_geometry r = in<jsrt_rec_geometry>(JSRT_SEC_GEOMETRY, i, "geometry");
+        if (r.kind == JSRT_GEOM_SDF) fail("SDF geometry is not supported by jsrt_blob_attach_obj_mtl_tex", -1);
+        if (r.kind == JSRT_GEOM_TRIANGLE)
+            r.index = append(O, JSRT_SEC_TRIANGLE, in<jsrt_rec_triangle>(JSRT_SEC_TRIANGLE, r.index, "triangle"));
+        return geom[i] = append(O, JSRT_SEC_GEOMETRY, r);
+    }
+    std::vector<int32_t> children(int32_t first, int32_t count) {
+        std::vector<int32_t> ids;
+        for (int32_t k = 0; k < count; ++k) ids.push_back(obj_index(in<int32_t>(JSRT_SEC_CHILD, first + k, "child")));
+        return ids;
+    }
+    int32_t push_children(const std::vector<int32_t> &ids) {
+        uint32_t c;
+        (void)recs<int32_t>(O, JSRT_SEC_CHILD, c);
+        for (int32_t x : ids) append(O, JSRT_SEC_CHILD, x);
+        return (int32_t)c;
+    }
+    int32_t bvh_index(int32_t i, int depth = 0) {
+        auto it = bvh.find(i);
+        if (it != bvh.end()) return it->second;
+        if (depth > 64) fail("BVH too deep", -1);
+        jsrt_rec_bvhnode r = in<jsrt_rec_bvhnode>(JSRT_SEC_BVHNODE, i, "BVH node");
+        const int32_t idx = append(O, JSRT_SEC_BVHNODE, r);  // (the record takes its place before its subtree)
+        bvh[i] = idx;
+        if (r.is_leaf) {
+            const std::vector<int32_t> ids = children(r.first_obj, r.n_obj);
+            r.first_obj = push_children(ids);
+        } else {
+            r.lesser = bvh_index(r.lesser, depth + 1);
+            r.greater = bvh_index(r.greater, depth + 1);
+        }
+        set(JSRT_SEC_BVHNODE, idx, r);
+        return idx;
+    }
+    int32_t obj_index(int32_t i, int depth = 0) {
+        auto it = obj.find(i);
+        if (it != obj.end()) return it->second;
+        if (depth > 64) fail("object nesting too deep", -1);
+        jsrt_rec_object r = in<jsrt_rec_object>(JSRT_SEC_OBJECT, i, "object");
+        r.matrix = matrix_index(r.matrix);
+        if (r.kind == JSRT_OBJ_PRIMITIVE) {
+            r.geometry = geom_index(r.geometry);
+            r.material = mat_index(r.material);
+        } else if (r.kind == JSRT_OBJ_BVH) r.bvh_root = bvh_index(r.bvh_root);
+        else if (r.kind == JSRT_OBJ_AGGREGATE || r.kind == JSRT_OBJ_TRANSFORMED) {
+            const std::vector<int32_t> ids = children(r.first_child, r.n_children);
+            r.first_child = push_children(ids);
+        } else fail("unsupported object kind", -1);
+        return obj[i] = append(O, JSRT_SEC_OBJECT, r);
+    }
+    Sections run() {
+        for (uint32_t tag : {JSRT_SEC_RENDERER, JSRT_SEC_CAMERA}) {
+            const int s = I.find(tag);
+            if (s < 0) fail("scene blob lacks renderer/camera", -1);
+            O.data[O.find(tag)] = I.data[s];
+            O.counts[O.find(tag)] = I.counts[s];
+        }
+        const int rs = I.find(JSRT_SEC_ROOT);
+        for (uint32_t k = 0; rs >= 0 && k < I.counts[rs]; ++k)
+            append(O, JSRT_SEC_ROOT, obj_index(in<int32_t>(JSRT_SEC_ROOT, (int32_t)k, "root")));
+        const int ls = I.find(JSRT_SEC_LIGHT);
+        for (uint32_t k = 0; ls >= 0 && k < I.counts[ls]; ++k) {
+            jsrt_rec_light r = in<jsrt_rec_light>(JSRT_SEC_LIGHT, (int32_t)k, "light");
+            r.color = mc_index(r.color);
+            append(O, JSRT_SEC_LIGHT, r);
+        }
+        // TEXR, TEXL, then PUVM, as the exporter orders its optional sections
+        Sections R;
+        auto move = [&](uint32_t tag) {
+            const int s = O.find(tag);
+            if (s < 0) return;
+            R.tags.push_back(tag);
+            R.counts.push_back(O.counts[s]);
+            R.data.push_back(std::move(O.data[s]));
+        };
+        for (uint32_t tag : {JSRT_SEC_RENDERER, JSRT_SEC_CAMERA, JSRT_SEC_MCOLOR, JSRT_SEC_MATERIAL, JSRT_SEC_GEOMETRY,
+                             JSRT_SEC_OBJECT, JSRT_SEC_MATRIX, JSRT_SEC_ROOT, JSRT_SEC_CHILD, JSRT_SEC_BVHNODE,
+                             JSRT_SEC_TRIANGLE, JSRT_SEC_LIGHT, JSRT_SEC_SDFNODE, JSRT_SEC_SDFGEOM, JSRT_SEC_TEXTURE,
+                             JSRT_SEC_TEXEL, JSRT_SEC_POSUV})
+            move(tag);
+        return R;
+    }
+};
+
 void splice(const void *blob, size_t n, const jsrt_mesh_options *opt, const char *obj, size_t obj_len,
-            const char *mtl_text, size_t mtl_len, std::vector<uint8_t> &out, jsrt_mesh_info *info) {
+            const char *mtl_text, size_t mtl_len, std::vector<uint8_t> &out, jsrt_mesh_info *info,
+            const jsrt_mesh_texture *textures = nullptr, size_t n_textures = 0, bool with_textures = false) {
     Sections S = read_blob(blob, n);
     MtlLib mtl;
+    std::map<std::string, int32_t> tex_by_name;  // textures[f] = ...: a later image of a name replaces an earlier one
+    MtlTextures MT;
+    if (with_textures) {
+        for (size_t i = 0; i < n_textures; ++i) {
+            if (!textures[i].name || !textures[i].rgba8 || textures[i].width < 1 || textures[i].height < 1)
+                fail("texture " + std::to_string(i) + " needs a name, RGBA8 bytes and a size of at least 1 x 1", -1);
+            tex_by_name[textures[i].name] = (int32_t)i;
+        }
+        MT.tex = textures;
+        MT.n = n_textures;
+        MT.mc.assign(n_textures, -1);
+    }
     for (size_t a = 0; a < mtl_len;) {  // one parseMtlFile per NUL-separated file, merged like Object.assign
         const char *z = (const char *)memchr(mtl_text + a, 0, mtl_len - a);
         const size_t b = z ? (size_t)(z - mtl_text) : mtl_len;
-        parse_mtl(mtl_text + a, b - a, mtl);
+        parse_mtl(mtl_text + a, b - a, mtl, with_textures ? &tex_by_name : nullptr);
         a = b + 1;
     }
     uint32_t n_obj, n_bvh, n_chld, n_geom, n_tri, n_mats;
@@ -687,6 +963,20 @@ void splice(const void *blob, size_t n, const jsrt_mesh_options *opt, const char
     // records: geometry + triangle + primitive per triangle, nodes in pre-order
     std::vector<int32_t> prim_of(tris.size()), mat_of(mtl.mats.size(), -1);
     int32_t white = -1;
+    if (with_textures) {
+        // SolidMaterialColor.White is one object in the reference: a Phong-family material of the blob names it
+        // under its reflectivity, Scaled(White, 0) (materials.js:202) -- the template's, when it came from an MTL
+        uint32_t nm, nc;
+        const jsrt_rec_material *Mt = recs<jsrt_rec_material>(S, JSRT_SEC_MATERIAL, nm);
+        const jsrt_rec_mcolor *Mc = recs<jsrt_rec_mcolor>(S, JSRT_SEC_MCOLOR, nc);
+        for (uint32_t k = 0; k < nm && white < 0; ++k) {
+            if (Mt[k].kind < JSRT_MAT_PHONG || Mt[k].kind > JSRT_MAT_PATH || Mt[k].reflect < 0 || (uint32_t)Mt[k].reflect >= nc) continue;
+            const jsrt_rec_mcolor &r = Mc[Mt[k].reflect];
+            if (r.kind != JSRT_MC_SCALED_SCALAR || r.a < 0 || (uint32_t)r.a >= nc) continue;
+            const jsrt_rec_mcolor &w = Mc[r.a];
+            if (w.kind == JSRT_MC_SOLID && w.len == 3 && w.vec[0] == 1.0f && w.vec[1] == 1.0f && w.vec[2] == 1.0f) white = r.a;
+        }
+    }
     for (size_t i = 0; i < tris.size(); ++i) {
         const Tri &t = tris[i];
         jsrt_rec_triangle tr;
@@ -715,7 +1005,7 @@ void splice(const void *blob, size_t n, const jsrt_mesh_options *opt, const char
         jsrt_rec_object o = tmpl;
         o.geometry = append(S, JSRT_SEC_GEOMETRY, g);
         if (t.mtl >= 0) {  // usemtl: the MTL material (one record per material used)
-            if (mat_of[t.mtl] < 0) mat_of[t.mtl] = mtl_material(S, mtl.mats[t.mtl], white);
+            if (mat_of[t.mtl] < 0) mat_of[t.mtl] = mtl_material(S, mtl.mats[t.mtl], white, with_textures ? &MT : nullptr);
             o.material = mat_of[t.mtl];
         }
         prim_of[i] = append(S, JSRT_SEC_OBJECT, o);
@@ -754,7 +1044,12 @@ void splice(const void *blob, size_t n, const jsrt_mesh_options *opt, const char
     jsrt_rec_object *Ow = recs<jsrt_rec_object>(S, JSRT_SEC_OBJECT, n_obj);
     for (uint32_t i = 0; i < n_obj; ++i)
         if (Ow[i].kind == JSRT_OBJ_BVH && Ow[i].bvh_root == r) Ow[i].bvh_root = (int32_t)base;
-    out = write_blob(S);
+    if (with_textures) {
+        Canon C(S);
+        out = write_blob(C.run());
+        bo = C.obj.count(bo) ? C.obj[bo] : -1;  // (its index in the re-laid blob)
+    } else
+        out = write_blob(S);
     if (info) {
         memset(info, 0, sizeof *info);
         info->triangles = (int64_t)tris.size();
@@ -784,6 +1079,31 @@ int jsrt_blob_attach_obj_mtl(const void *blob, size_t n, const char *obj_text, s
         std::vector<uint8_t> out;
         if (!mtl_text && mtl_len) return jsrt::record_error(-1, "mtl_text is NULL");
         splice(blob, n, options, obj_text ? obj_text : "", obj_len, mtl_text, mtl_len, out, info);
+        void *p = malloc(out.size());
+        if (!p) return jsrt::record_error(-4, "out of host memory");
+        memcpy(p, out.data(), out.size());
+        *out_blob = p;
+        *out_n = out.size();
+        return 0;
+    } catch (const Fail &f) {
+        return jsrt::record_error(f.code, f.msg);
+    } catch (const std::bad_alloc &) {
+        return jsrt::record_error(-4, "out of host memory");
+    }
+}
+
+int jsrt_blob_attach_obj_mtl_tex(const void *blob, size_t n, const char *obj_text, size_t obj_len, const char *mtl_text,
+                                 size_t mtl_len, const jsrt_mesh_texture *textures, size_t n_textures,
+                                 const jsrt_mesh_options *options, void **out_blob, size_t *out_n, jsrt_mesh_info *info) {
+    if (!out_blob || !out_n) return jsrt::record_error(-1, "out_blob / out_n is NULL");
+    *out_blob = nullptr;
+    *out_n = 0;
+    if (!obj_text && obj_len) return jsrt::record_error(-1, "obj_text is NULL");
+    if (!mtl_text && mtl_len) return jsrt::record_error(-1, "mtl_text is NULL");
+    if (!textures && n_textures) return jsrt::record_error(-1, "textures is NULL");
+    try {
+        std::vector<uint8_t> out;
+        splice(blob, n, options, obj_text ? obj_text : "", obj_len, mtl_text, mtl_len, out, info, textures, n_textures, true);
         void *p = malloc(out.size());
         if (!p) return jsrt::record_error(-4, "out of host memory");
         memcpy(p, out.data(), out.size());

@@ -35,6 +35,7 @@ struct MtlMat {
     bool ka = false, kd = false, ks = false;
     float Ka[3] = {0, 0, 0}, Kd[3] = {0, 0, 0}, Ks[3] = {0, 0, 0};
     double Ns = 0.0 / 0.0;  // NaN: absent (`data.Ns || 0`)
+    int32_t map_ka = -1, map_kd = -1, map_ks = -1;  // map_Ka / map_Kd / map_Ks: index into the supplied textures
 };
 struct MtlLib {
     std::vector<MtlMat> mats;
@@ -43,8 +44,9 @@ struct MtlLib {
 
 // Triangle constructor (geometry.js:335-354) in the reference's numeric model.
 void triangle_ctor(Tri &t);
-// parseMtlFile (objloader.js:58-123), merged into `lib`.
-void parse_mtl(const char *text, size_t n, MtlLib &lib);
+// parseMtlFile (objloader.js:58-123), merged into `lib`.  textures: the decoded images the caller supplies, by
+// file name (null: map_Ka / map_Kd / map_Ks are refused, jsrt_blob_attach_obj_mtl).
+void parse_mtl(const char *text, size_t n, MtlLib &lib, const std::map<std::string, int32_t> *textures = nullptr);
 // parseObjFile (objloader.js:144-221) with loadObjFile's minArea filter (:224-231); prim_transform
 // (16 doubles, row-major) is the per-triangle Primitive transform the bounds are taken under, or null.
 void parse_obj(const char *text, size_t n, double min_area, const double *prim_transform, const MtlLib &mtl,

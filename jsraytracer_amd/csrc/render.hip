@@ -524,6 +524,25 @@ hipError_t material_data_rays(const DScene &S, const float *d_rays, uint32_t n, 
     return hipGetLastError();
 }
 
+#define JSRT_MUV_EXTERN(PFV) \
+    extern template void material_uv_pf<PFV>(const DScene &, const float *, uint32_t, float *, int32_t *, hipStream_t);
+JSRT_MUV_EXTERN(PF_ANALYTIC)
+JSRT_MUV_EXTERN(PF_MESH)
+JSRT_MUV_EXTERN(PF_SDF)
+JSRT_MUV_EXTERN(PF_ALL)
+#undef JSRT_MUV_EXTERN
+
+hipError_t material_uv_rays(const DScene &S, const float *d_rays, uint32_t n, float *d_uv, int32_t *d_has, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    switch (S.profile) {
+    case PF_ANALYTIC: material_uv_pf<PF_ANALYTIC>(S, d_rays, n, d_uv, d_has, st); break;
+    case PF_MESH: material_uv_pf<PF_MESH>(S, d_rays, n, d_uv, d_has, st); break;
+    case PF_SDF: material_uv_pf<PF_SDF>(S, d_rays, n, d_uv, d_has, st); break;
+    default: material_uv_pf<PF_ALL>(S, d_rays, n, d_uv, d_has, st); break;
+    }
+    return hipGetLastError();
+}
+
 // SDF.distance of SDF geometry g's root (sdf.js:53-74) at points (f32 x 4, w = 1): the same program VM
 // the render's march runs (jsrt_sdf_distance)
 __global__ __launch_bounds__(256) void k_sdf_distance(DScene S, int g, const float *pts, uint32_t n, double *out) {

@@ -205,6 +205,10 @@ hipError_t material_data_rays(const DScene &S, const float *d_rays, uint32_t n, 
                               float *d_nrm, float *d_pos, float *d_uv, float *d_bary, float *d_bc, hipStream_t st);
 // SDF.distance of SDF geometry g's root at n local points (f32 x 4) (jsrt_sdf_distance).
 hipError_t sdf_distance_points(const DScene &S, int g, const float *d_pts, uint32_t n, double *d_out, hipStream_t st);
+// The UV pair the base material's colour chains read at each ray's closest hit (jsrt_material_uv): n x 2 f32 and
+// n flags (0: a miss, or a hit whose material_data has no UV; the pair is NaN).
+hipError_t material_uv_rays(const DScene &S, const float *d_rays, uint32_t n, float *d_uv, int32_t *d_has, hipStream_t st);
+
 // MaterialColor.color({UV}) of MCOL record mc at n UV pairs (f32 x 2) -> r, g, b (f32 x 3) (jsrt_material_color).
 hipError_t material_color_uvs(const DScene &S, int mc, const float *d_uv, uint32_t n, float *d_rgb, hipStream_t st);
 

@@ -444,18 +444,24 @@ __device__ __forceinline__ void surface_data(const DScene &S, const Hit &h, F3 o
 // stored) and leaves in LDS, in column threadIdx.x of `fixl` [5][256]: fix0, fix1 (1 + the pick's RNG call,
 // bit 31 = scattered about -N, the refraction side; 0 = none) and the node's N.  k_shade recomputes those
 // directions at its tail (fix_child_dirs), so nothing of it is live in registers through the stores.
+// PUV (a scene with a PositionalUVMaterial, DScene::has_posuv): a MATF_PUV material's (u, v) are the mapping of the
+// hit point (posuv_map.h) and its geometric UV is dead (need_uv false: no cart_to_sph, no atan2).
 constexpr uint32_t INFO_FIX = 1u << 30;
-template <int PF, bool TEX>
+template <int PF, bool TEX, bool PUV = false>
 __device__ __forceinline__ int shade_node(const DScene &S, bool lit, const Hit &h, F3 o, F3 d, uint32_t addr,
                                           uint32_t key, NodeOut &out, Child &ch0, Child &ch1, uint32_t *fixl,
                                           bool force_fix) {
     const DPrim &P = S.prims[h.prim];
     Surface sf;
-    surface_data<PF, false>(S, h, o, d, (S.mat_flags[P.material] & MATF_UV) != 0, sf);
+    const bool puv = PUV && (S.mat_flags[P.material] & MATF_PUV) != 0;
+    surface_data<PF, false>(S, h, o, d, (S.mat_flags[P.material] & MATF_UV) != 0 && !puv, sf);
     const F3 N = sf.N, basecolor = sf.basecolor;
-    const float u = sf.u, v = sf.v;
+    float u = sf.u, v = sf.v;
     ShadeData sd;
     sd.pos = ray_point(o, d, h.t);  // material_data.position = ray.getPoint(distance)
+    if constexpr (PUV) {  // PositionalUVMaterial.color (materials.js:188-191): data.UV overwritten from the position
+        if (puv && (S.mat_flags[P.material] & MATF_UV)) posuv_map(S.puv[P.material], sd.pos.x, sd.pos.y, sd.pos.z, u, v);
+    }
     out.h.pos = sd.pos;
     out.h.addr = addr;
     out.h.key = key;
@@ -813,6 +819,7 @@ __device__ __forceinline__ void stab_bind(DScene &SL, const uint4 *lds, bool sha
     SL.shade0 = reinterpret_cast<const double *>(sb + SL.stab_off[STAB_SHADE0]);
     SL.shadeI = reinterpret_cast<const double *>(sb + SL.stab_off[STAB_SHADEI]);
     SL.prim_lit = reinterpret_cast<const int32_t *>(sb + SL.stab_off[STAB_PRIM_LIT]);
+    SL.puv = reinterpret_cast<const jsrt_rec_posuv *>(sb + SL.stab_off[STAB_POSUV]);
 }
 // The first `words` 16-B words of DScene::stab copied into the block's dynamic LDS and bound in SL (the kernel's
 // own copy of S).  Every thread of the block must call it (a barrier).
@@ -830,7 +837,10 @@ __device__ __forceinline__ void stab_stage(const DScene &S, DScene &SL, int word
 // texture_sample.h).  A template parameter of the kernel, so the instantiations every other scene launches hold no
 // sampler and keep their registers (profiles/texture_kernel_resources.txt; the same body behind a forceinline
 // wrapper cost k_shade<PF_ANALYTIC, false, false> a VGPR and the SDF chain two spills).
-template <int PF, bool CHAIN, bool STAGE, bool TEX = false>
+// PUV (a scene with a PositionalUVMaterial, DScene::has_posuv): shade_node's position-mapped UV, a template parameter
+// for the same reason; such a scene always runs <TEX = true, PUV = true>, so the class costs one more instantiation
+// per schedule, not two.
+template <int PF, bool CHAIN, bool STAGE, bool TEX = false, bool PUV = false>
 __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
                                                     : (PF & PF_SDF) ? JSRT_SHADE_OCC_SDF : JSRT_SHADE_OCC) SHADE_ATTR void k_shade(
     DScene S, WArgs W, int L, int child_depth) {
@@ -887,7 +897,7 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
             rkey = W.key[r];
         }
         const Hit h{rt, prim, rctx};
-        nchild = shade_node<PF, TEX>(SL, W.ns > 0, h, ro, rd, raddr, rkey, out, ch0, ch1, fixl, W.force_fix != 0);
+        nchild = shade_node<PF, TEX, PUV>(SL, W.ns > 0, h, ro, rd, raddr, rkey, out, ch0, ch1, fixl, W.force_fix != 0);
         out.h.node = CHAIN ? slot : q;  // (k_shadow: node base + this)
         out.h.mask = (uint32_t)S.grid_cells;  // every root
         if (W.bucket && (out.info & INFO_LIT)) {  // the lit node's hand-off slot, ranked by k_extend
@@ -1406,6 +1416,47 @@ void material_data_pf(const DScene &S, const float *rays, uint32_t n, double *t,
                        bary, bc);
 }
 
+// The UV pair the base material's colour chains read at each ray's closest hit (jsrt_material_uv): shade_node's own
+// steps -- surface_data, then a MATF_PUV material's mapping of the hit point (posuv_map.h) -- so a mapping error
+// shows per hit.  Unlike shade_node, which asks surface_data for the geometric UV only where the material reads it
+// (MATF_UV), the geometric UV of an unwrapped hit is always computed here: the reference's data.UV exists whether
+// or not a colour chain reads it.  has_uv: 0 on a miss and where the reference's data.UV is undefined (an AABB, an SDF
+// without UV, a triangle without `vt`, none of them under a wrapper); the pair is NaN there.
+template <int PF>
+__global__ __launch_bounds__(256) void k_material_uv(DScene S, const float *rays, uint32_t n, float *uv, int32_t *has) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float *r = rays + 6 * (size_t)i;
+    const F3 o = f3(r[0], r[1], r[2]), d = f3(r[3], r[4], r[5]);
+    const Hit h = world_cast<PF, false>(S, o, d, 0.0, DINF, true);
+    const float nan = __builtin_nanf("");
+    float u = nan, v = nan;
+    int32_t hu = 0;
+    if (h.prim >= 0) {
+        const DPrim &P = S.prims[h.prim];
+        const bool puv = S.has_posuv && (S.mat_flags[P.material] & MATF_PUV) != 0;
+        Surface sf;
+        surface_data<PF, false>(S, h, o, d, !puv, sf);
+        if (puv) {
+            const F3 p = ray_point(o, d, h.t);
+            posuv_map(S.puv[P.material], p.x, p.y, p.z, u, v);
+            hu = 1;
+        } else if (sf.has_uv) {
+            u = sf.u;
+            v = sf.v;
+            hu = 1;
+        }
+    }
+    uv[2 * (size_t)i] = u;
+    uv[2 * (size_t)i + 1] = v;
+    has[i] = hu;
+}
+template <int PF>
+void material_uv_pf(const DScene &S, const float *rays, uint32_t n, float *uv, int32_t *has, hipStream_t st) {
+    const size_t lds = (PF & (PF_BVH | PF_AGG)) ? bvh_lds_bytes(S, 256) : 0;
+    hipLaunchKernelGGL((k_material_uv<PF>), dim3(grid_ub(n)), dim3(256), lds, st, S, rays, n, uv, has);
+}
+
 // Enqueues one batch without a host round trip.  Chain: every level has exactly npaths slots.
 // Tree: level L's launches cover bound[L] rays (the real count is on the device and surplus
 // blocks exit at once; a count above the bound sets LVL_UNDER and the frame is redone);
@@ -1452,7 +1503,12 @@ void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t
         timed(KT_SHADE, [&] {
             const bool staged = PF == PF_ANALYTIC && S.stab_words > 0;  // the LDS-staged shading tables
             const size_t sl = staged ? (size_t)S.stab_words * 16 : 0;
-            if (S.has_textures) {  // the TEX instantiations: the texture sampler in the colour chains
+            if (S.has_posuv) {  // the PUV instantiations: position-mapped UVs (and the sampler, should a chain need it)
+                if (staged)
+                    hipLaunchKernelGGL((k_shade<PF, CHAIN, PF == PF_ANALYTIC, true, true>), dim3(grid_ub(ub)), dim3(256), sl, st, S, W, L, child_depth);
+                else
+                    hipLaunchKernelGGL((k_shade<PF, CHAIN, false, true, true>), dim3(grid_ub(ub)), dim3(256), 0, st, S, W, L, child_depth);
+            } else if (S.has_textures) {  // the TEX instantiations: the texture sampler in the colour chains
                 if (staged)
                     hipLaunchKernelGGL((k_shade<PF, CHAIN, PF == PF_ANALYTIC, true>), dim3(grid_ub(ub)), dim3(256), sl, st, S, W, L, child_depth);
                 else

@@ -26,5 +26,6 @@ template void cast_rays_pf<JSRT_PF>(const DScene &, const float *, uint32_t, dou
                                    hipStream_t);
 template void material_data_pf<JSRT_PF>(const DScene &, const float *, uint32_t, double *, int32_t *, float *, float *,
                                         float *, float *, float *, hipStream_t);
+template void material_uv_pf<JSRT_PF>(const DScene &, const float *, uint32_t, float *, int32_t *, hipStream_t);
 #endif
 }  // namespace jsrt

@@ -31,7 +31,8 @@ struct Blob {
     const jsrt_rec_sdfgeom *sdfg = nullptr;
     const jsrt_rec_texture *tex = nullptr;
     const uint8_t *texl = nullptr;
-    uint32_t n_tex = 0, n_texl = 0;
+    const jsrt_rec_posuv *puv = nullptr;
+    uint32_t n_tex = 0, n_texl = 0, n_puv = 0;
     uint32_t n_mc = 0, n_mat = 0, n_geom = 0, n_obj = 0, n_mats = 0, n_root = 0, n_chld = 0, n_bvh = 0, n_tri = 0,
              n_lite = 0, n_sdf = 0, n_sdfg = 0;
 };
@@ -79,6 +80,7 @@ Blob parse(const void *data, size_t nbytes) {
         case JSRT_SEC_SDFGEOM: bind(s, b, B.sdfg, B.n_sdfg, "SDFG"); break;
         case JSRT_SEC_TEXTURE: bind(s, b, B.tex, B.n_tex, "TEXR"); break;
         case JSRT_SEC_TEXEL: bind(s, b, B.texl, B.n_texl, "TEXL"); break;
+        case JSRT_SEC_POSUV: bind(s, b, B.puv, B.n_puv, "PUVM"); break;
         default: break;  // unknown sections are ignored (forward compatible)
         }
     }
@@ -203,6 +205,7 @@ struct Loader {
     std::vector<LBox> prim_box;                          // local bound per DPrim
     double cur_leaf_kappa = 1;
     std::unordered_map<int32_t, double> bvh_leaf_kappa;  // BVHN root -> max leaf condition number
+    std::vector<int32_t> mat_of_blob;                    // MATL idx -> index in S.mat (wrappers flattened)
 
     Loader(const Blob &b, HostScene &s) : B(b), S(s) {}
 
@@ -263,6 +266,56 @@ struct Loader {
     void refuse_texture(int32_t chain, const char *owner, const char *slot, const char *why) {
         if (mc_has_texture(chain))
             fail(std::string("TextureMaterialColor is not supported in ") + owner + "." + slot + ": " + why);
+    }
+
+    // PositionalUVMaterial (materials.js:177-193): each wrapper overwrites data.UV and delegates, so the colour chains
+    // of the innermost base material read the INNERMOST wrapper's mapping, whatever the outer ones hold.  A chain of
+    // wrappers becomes one device material: the base's record (its slot rules and MATF_UV judged on it above) with
+    // MATF_PUV and a mapping in S.puv, one entry per distinct pair (base, mapping).
+    void check_posuv(const jsrt_rec_posuv &R) {
+        const struct { const char *name; uint32_t len; } f[3] = {{"origin", R.origin_len}, {"u_axis", R.u_len}, {"v_axis", R.v_len}};
+        for (const auto &x : f)
+            if (x.len != 3 && x.len != 4)
+                fail(std::string("PositionalUVMaterial.") + x.name + " must have 3 or 4 components (has " +
+                     std::to_string(x.len) + ")");
+        for (int k = 1; k < 3; ++k)
+            if (f[k].len > R.origin_len)
+                fail(std::string("PositionalUVMaterial.") + f[k].name + " has " + std::to_string(f[k].len) +
+                     " components but origin has " + std::to_string(R.origin_len) +
+                     ": the reference reads delta[3] of a 3-component delta (a NaN UV)");
+    }
+    void posuv_materials() {
+        std::map<std::pair<int32_t, std::string>, int32_t> seen;
+        for (uint32_t i = 0; i < B.n_mat; ++i) {
+            if (B.mat[i].kind != JSRT_MAT_POSITIONAL_UV) continue;
+            int32_t cur = (int32_t)i, map = -1;
+            for (int depth = 0; B.mat[cur].kind == JSRT_MAT_POSITIONAL_UV;) {
+                if (++depth > 8) fail("PositionalUVMaterial.baseMaterial nesting too deep (more than 8 wrappers)");
+                const jsrt_rec_material &M = B.mat[cur];
+                if (M.color < 0 || (uint32_t)M.color >= B.n_puv) fail("PositionalUVMaterial mapping index out of range");
+                check_posuv(B.puv[M.color]);
+                map = M.color;  // the innermost wrapper's is the one the base sees
+                if (M.base < 0 || (uint32_t)M.base >= B.n_mat) fail("PositionalUVMaterial.baseMaterial index out of range");
+                cur = M.base;
+            }
+            const int32_t base = mat_of_blob[cur];
+            const auto key = std::make_pair(base, std::string((const char *)&B.puv[map], sizeof(jsrt_rec_posuv)));
+            auto it = seen.find(key);
+            if (it == seen.end()) {
+                it = seen.emplace(key, (int32_t)S.mat.size()).first;
+                S.puv.resize(S.mat.size(), jsrt_rec_posuv{});
+                S.puv.push_back(B.puv[map]);
+                const jsrt_rec_material bm = S.mat[base];
+                S.mat.push_back(bm);
+                S.mat_flags.push_back(S.mat_flags[base] | MATF_PUV);
+            }
+            mat_of_blob[i] = it->second;
+        }
+        if (!S.puv.empty()) {
+            S.puv.resize(S.mat.size(), jsrt_rec_posuv{});
+            S.has_posuv = 1;
+        }
+        if (S.mat.size() >= ((size_t)1 << 20)) fail("more than 2^20 materials");
     }
 
     void shading_matrices() {
@@ -336,7 +389,7 @@ struct Loader {
         memcpy(p.inv, M.inv, sizeof p.inv);
         p.gkind = (int32_t)G.kind;
         p.gindex = -1;
-        p.material = O.material;
+        p.material = mat_of_blob[O.material];
         p.casts_shadow = O.casts_shadow ? 1 : 0;
         switch (G.kind) {
         case JSRT_GEOM_PLANE:
@@ -1028,9 +1081,12 @@ struct Loader {
         // the shadow hand-off packs the material index into 20 bits beside the grid mask and its plane flags
         // (render_levels.h store_hand: mat << 8 | mask | HAND_*)
         if (B.n_mat >= (1u << 20)) fail("more than 2^20 materials");
+        mat_of_blob.assign(B.n_mat, -1);
         for (uint32_t i = 0; i < B.n_mat; ++i) {
             const jsrt_rec_material &M = B.mat[i];
-            if (M.kind < JSRT_MAT_PHONG || M.kind > JSRT_MAT_TRANSPARENT) fail("unsupported material kind");
+            if (M.kind < JSRT_MAT_PHONG || M.kind > JSRT_MAT_POSITIONAL_UV) fail("unsupported material kind");
+            if (M.kind == JSRT_MAT_POSITIONAL_UV) continue;  // flattened below, onto its innermost base
+            mat_of_blob[i] = (int32_t)S.mat.size();
             static const char *const kind_name[] = {"", "PhongMaterial", "FresnelPhongMaterial", "PhongPathTracingMaterial",
                                                     "SolidColorMaterial", "TransparentMaterial"};
             const char *kn = kind_name[M.kind];
@@ -1055,6 +1111,7 @@ struct Loader {
                 if (mc_uses_uv(root)) fl |= MATF_UV;
             S.mat_flags.push_back(fl);
         }
+        posuv_materials();
         for (uint32_t i = 0; i < B.n_mc; ++i) {
             S.mc.push_back(B.mc[i]);
             if (B.mc[i].kind == JSRT_MC_TEXTURE) {  // (a record no material uses is checked too: jsrt_material_color)

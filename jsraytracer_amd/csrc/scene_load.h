@@ -33,6 +33,8 @@ struct HostScene {
     std::vector<jsrt_rec_texture> tex;  // the blob's TEXR descriptors ...
     std::vector<uint8_t> texels;        // ... and TEXL bytes (empty without textures)
     std::vector<double> tex_q255;       // byte / 255 (texture_sample.h tex_q255_table; empty without textures)
+    int32_t has_posuv = 0;              // some material is a flattened PositionalUVMaterial (the PUV instantiations)
+    std::vector<jsrt_rec_posuv> puv;    // per material: its mapping (MATF_PUV ones; empty without the class)
     std::vector<DLight> lights;
     std::vector<int32_t> sample_light, sample_call;  // per light sample of a node
     int32_t light_draws = 0;

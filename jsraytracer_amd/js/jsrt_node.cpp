@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/jsrt.h"
 #include "../../include/jsrt_json.h"
@@ -331,7 +332,9 @@ napi_value Render(napi_env env, napi_callback_info info) {
     return promise;
 }
 
-// attachObj(blob, objText, {bvhObject, minArea}?) -> {blob: Buffer, triangles, nodes, maxDepth}
+// attachObj(blob, objText, {bvhObject, minArea, mtl, textures}?) -> {blob: Buffer, triangles, nodes, maxDepth}
+// textures: {name: {width, height, data: Uint8Array | Uint8ClampedArray (RGBA8)}} for the MTL's map_Ka / map_Kd /
+// map_Ks statements (jsrt_blob_attach_obj_mtl_tex)
 // loadObjFile + BVHAggregate.build natively (include/jsrt_mesh.h; objloader.js:224-231, aggregates.js:33-41)
 // string (UTF-8) or Uint8Array/Buffer contents
 bool get_text(napi_env env, napi_value v, std::string &out) {
@@ -365,6 +368,9 @@ napi_value AttachObj(napi_env env, napi_callback_info info) {
         return nullptr;
     }
     jsrt_mesh_options opt{-1, 0, 0.00001};
+    bool with_tex = false;
+    std::vector<std::string> tex_names;
+    std::vector<jsrt_mesh_texture> tex;
     if (argc > 2) {
         napi_valuetype t;
         napi_typeof(env, argv[2], &t);
@@ -396,14 +402,50 @@ napi_value AttachObj(napi_env env, napi_callback_info info) {
                     mtl += one;
                 }
             }
+            if (napi_has_named_property(env, argv[2], "textures", &has) == napi_ok && has &&
+                napi_get_named_property(env, argv[2], "textures", &v) == napi_ok) {
+                napi_valuetype tv;
+                napi_typeof(env, v, &tv);
+                napi_value names;
+                uint32_t n = 0;
+                if (tv != napi_object || napi_get_property_names(env, v, &names) != napi_ok ||
+                    napi_get_array_length(env, names, &n) != napi_ok) {
+                    napi_throw_type_error(env, "JSRT", "attachObj: opts.textures must be an object {name: {width, height, data}}");
+                    return nullptr;
+                }
+                with_tex = true;
+                tex_names.resize(n);
+                for (uint32_t i = 0; i < n; ++i) {
+                    napi_value key, img, f;
+                    jsrt_mesh_texture t{nullptr, nullptr, 0, 0};
+                    void *px = nullptr;
+                    size_t pn = 0;
+                    napi_get_element(env, names, i, &key);
+                    bool ok = get_text(env, key, tex_names[i]) && napi_get_property(env, v, key, &img) == napi_ok &&
+                              napi_get_named_property(env, img, "width", &f) == napi_ok &&
+                              napi_get_value_uint32(env, f, &t.width) == napi_ok &&
+                              napi_get_named_property(env, img, "height", &f) == napi_ok &&
+                              napi_get_value_uint32(env, f, &t.height) == napi_ok &&
+                              napi_get_named_property(env, img, "data", &f) == napi_ok && get_bytes(env, f, &px, &pn);
+                    if (!ok || t.width < 1 || t.height < 1 || pn != (size_t)t.width * t.height * 4) {
+                        napi_throw_type_error(env, "JSRT", "attachObj: a texture needs width, height and data of width * height * 4 bytes");
+                        return nullptr;
+                    }
+                    t.rgba8 = (const uint8_t *)px;
+                    tex.push_back(t);
+                }
+                for (uint32_t i = 0; i < n; ++i) tex[i].name = tex_names[i].c_str();
+            }
         }
     }
     void *out = nullptr;
     size_t out_n = 0;
     jsrt_mesh_info mi;
-    if (jsrt_blob_attach_obj_mtl(data, len, text.data(), text.size(), mtl.data(), mtl.size(), &opt, &out, &out_n,
-                                 &mi) != 0)
-        return throw_jsrt(env, "jsrt_blob_attach_obj");
+    const int rc = with_tex ? jsrt_blob_attach_obj_mtl_tex(data, len, text.data(), text.size(), mtl.data(), mtl.size(), tex.data(),
+                                                           tex.size(), &opt, &out, &out_n, &mi)
+                            : jsrt_blob_attach_obj_mtl(data, len, text.data(), text.size(), mtl.data(), mtl.size(), &opt, &out,
+                                                       &out_n, &mi);
+    if (rc != 0) return throw_jsrt(env, "jsrt_blob_attach_obj");
     napi_value buf, o, v;
     void *dst = nullptr;
     napi_status st = napi_create_buffer_copy(env, out_n, out, &dst, &buf);

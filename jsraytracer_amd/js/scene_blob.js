@@ -16,7 +16,7 @@
 
 const SEC = {};
 function fourcc(s) { return s.charCodeAt(0) | (s.charCodeAt(1) << 8) | (s.charCodeAt(2) << 16) | (s.charCodeAt(3) << 24) >>> 0; }
-for (const t of ["RNDR", "CAMR", "MCOL", "MATL", "GEOM", "OBJS", "MATS", "ROOT", "CHLD", "BVHN", "TRIS", "LITE", "SDFN", "SDFG", "TEXR", "TEXL"])
+for (const t of ["RNDR", "CAMR", "MCOL", "MATL", "GEOM", "OBJS", "MATS", "ROOT", "CHLD", "BVHN", "TRIS", "LITE", "SDFN", "SDFG", "TEXR", "TEXL", "PUVM"])
     SEC[t] = fourcc(t) >>> 0;
 
 const K = {
@@ -24,7 +24,7 @@ const K = {
     CAMERA_PERSPECTIVE: 0, CAMERA_DOF: 1,
     MC_SOLID: 1, MC_SCALED_SCALAR: 2, MC_SCALED_VEC: 3, MC_CHECKER: 4, MC_TEXTURE: 5,
     TEX_BILINEAR: 0, TEX_NEAREST: 1,
-    MAT_PHONG: 1, MAT_FRESNEL: 2, MAT_PATH: 3, MAT_SOLID: 4, MAT_TRANSPARENT: 5,
+    MAT_PHONG: 1, MAT_FRESNEL: 2, MAT_PATH: 3, MAT_SOLID: 4, MAT_TRANSPARENT: 5, MAT_POSITIONAL_UV: 6,
     GEOM_PLANE: 1, GEOM_SQUARE: 2, GEOM_CIRCLE: 3, GEOM_SPHERE: 4, GEOM_CYLINDER: 5, GEOM_AABB: 6,
     GEOM_TRIANGLE: 7, GEOM_SDF: 8,
     OBJ_PRIMITIVE: 1, OBJ_AGGREGATE: 2, OBJ_BVH: 3, OBJ_TRANSFORMED: 4,
@@ -88,6 +88,8 @@ class SceneBlobWriter {
         this.textures = [];
         this.texels = [];
         this.texelBytes = 0;
+        // PositionalUVMaterial mappings (PUVM): likewise written only when a scene has the class
+        this.posuvs = [];
         this.maps = { tex: new Map(), mc: new Map(), mat: new Map(), geom: new Map(), obj: new Map(), bvh: new Map(), matrix: new Map(),
                       matrixBytes: new Map(), sdf: new Map(), sdfgeom: new Map() };
     }
@@ -160,6 +162,18 @@ class SceneBlobWriter {
     matIndex(m) {
         if (this.maps.mat.has(m)) return this.maps.mat.get(m);
         const r = new Rec(64);
+        if (isA(m, "PositionalUVMaterial")) {  // materials.js:177-193: the base material, then the wrapper's record
+            const base = this.matIndex(m.baseMaterial);
+            const o = assertVec(m.origin, "PositionalUVMaterial.origin"), u = assertVec(m.u_axis, "PositionalUVMaterial.u_axis"),
+                  v = assertVec(m.v_axis, "PositionalUVMaterial.v_axis");
+            const p = new Rec(64).vec(0, o).vec(16, u).vec(32, v).u32(48, o.length).u32(52, u.length).u32(56, v.length);
+            r.u32(0, K.MAT_POSITIONAL_UV);
+            for (let i = 1; i < 8; ++i) r.i32(4 * i, -1);
+            r.i32(4, base).i32(28, this.posuvs.push(p) - 1);
+            const idx = this.push("MATL", r);
+            this.maps.mat.set(m, idx);
+            return idx;
+        }
         let kind;
         if (isA(m, "PhongPathTracingMaterial")) kind = K.MAT_PATH;
         else if (isA(m, "FresnelPhongMaterial")) kind = K.MAT_FRESNEL;
@@ -376,8 +390,8 @@ class SceneBlobWriter {
 
     serialize() {
         const tags = Object.keys(REC_SIZE);
-        const ntex = this.textures.length;
-        const header = 16 + 24 * (tags.length + (ntex ? 2 : 0));
+        const ntex = this.textures.length, npuv = this.posuvs.length;
+        const header = 16 + 24 * (tags.length + (ntex ? 2 : 0) + (npuv ? 1 : 0));
         let off = (header + 7) & ~7;
         const descs = [];
         for (const t of tags) {
@@ -387,10 +401,12 @@ class SceneBlobWriter {
         }
         const texr = off, texl = texr + 32 * ntex;
         if (ntex) off = texl + ((this.texelBytes + 7) & ~7);
+        const puvm = off;
+        off += 64 * npuv;
         const out = Buffer.alloc(off);
         out.writeUInt32LE(0x5452534A, 0);
         out.writeUInt32LE(1, 4);
-        out.writeUInt32LE(tags.length + (ntex ? 2 : 0), 8);
+        out.writeUInt32LE(tags.length + (ntex ? 2 : 0) + (npuv ? 1 : 0), 8);
         out.writeUInt32LE(0, 12);
         descs.forEach(([t, n, o, b], i) => {
             const p = 16 + 24 * i;
@@ -410,6 +426,13 @@ class SceneBlobWriter {
             this.textures.forEach((rec, i) => Buffer.from(rec.buf).copy(out, texr + 32 * i));
             let q = texl;
             for (const b of this.texels) { b.copy(out, q); q += b.length; }
+        }
+        if (npuv) {
+            const p = 16 + 24 * (tags.length + (ntex ? 2 : 0));
+            out.writeUInt32LE(SEC.PUVM, p); out.writeUInt32LE(npuv, p + 4);
+            out.writeUInt32LE(puvm, p + 8); out.writeUInt32LE(0, p + 12);
+            out.writeUInt32LE(64 * npuv, p + 16); out.writeUInt32LE(0, p + 20);
+            this.posuvs.forEach((rec, i) => Buffer.from(rec.buf).copy(out, puvm + 64 * i));
         }
         return out;
     }

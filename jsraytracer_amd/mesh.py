@@ -19,17 +19,32 @@ def _bytes(t):
     return t.encode() if isinstance(t, str) else bytes(t)
 
 
-def attach_obj(blob, obj_text, bvh_object=-1, min_area=0.00001, mtl_texts=()):
+def attach_obj(blob, obj_text, bvh_object=-1, min_area=0.00001, mtl_texts=(), textures=None):
     """Return (new_blob: bytes, info: dict) with the OBJ's triangles and their BVH spliced into the
     BVHAggregate object `bvh_object` (< 0: the first one).  `mtl_texts`: the OBJ's mtllib files'
-    texts in mtllib order.  Raises JsrtError as the reference throws."""
+    texts in mtllib order.  `textures`: {file name: H x W x 4 uint8 image} for the MTL's map_Ka / map_Kd /
+    map_Ks statements (include/jsrt_mesh.h jsrt_blob_attach_obj_mtl_tex; the result is then laid out as the
+    exporter writes the same scene); without it those statements are refused.  Raises JsrtError as the
+    reference throws."""
     L = _native.lib()
     obj_text, blob = _bytes(obj_text), bytes(blob)
     mtl = b"\0".join(_bytes(t) for t in mtl_texts)
     opt = _native.MeshOptions(int(bvh_object), 0, float(min_area))
     out, n, info = ctypes.c_void_p(), ctypes.c_size_t(), _native.MeshInfo()
-    rc = L.jsrt_blob_attach_obj_mtl(blob, len(blob), obj_text, len(obj_text), mtl, len(mtl), ctypes.byref(opt),
-                                    ctypes.byref(out), ctypes.byref(n), ctypes.byref(info))
+    if textures is not None:
+        import numpy as np
+        imgs = [(_bytes(k), np.ascontiguousarray(v, np.uint8)) for k, v in textures.items()]
+        for k, v in imgs:
+            if v.ndim != 3 or v.shape[2] != 4 or v.shape[0] < 1 or v.shape[1] < 1:
+                raise ValueError(f"texture {k!r} must be an H x W x 4 uint8 image")
+        arr = (_native.MeshTexture * max(1, len(imgs)))(*[_native.MeshTexture(k, v.ctypes.data, v.shape[1], v.shape[0])
+                                                          for k, v in imgs])
+        rc = _native.mesh_texture_api().jsrt_blob_attach_obj_mtl_tex(
+            blob, len(blob), obj_text, len(obj_text), mtl, len(mtl), arr, len(imgs), ctypes.byref(opt), ctypes.byref(out),
+            ctypes.byref(n), ctypes.byref(info))
+    else:
+        rc = L.jsrt_blob_attach_obj_mtl(blob, len(blob), obj_text, len(obj_text), mtl, len(mtl), ctypes.byref(opt),
+                                        ctypes.byref(out), ctypes.byref(n), ctypes.byref(info))
     _native.check(rc, "jsrt_blob_attach_obj")
     try:
         data = ctypes.string_at(out, n.value)

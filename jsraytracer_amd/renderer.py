@@ -92,6 +92,18 @@ class Scene:
               "jsrt_material_data")
         return out
 
+    def material_uv(self, rays):
+        """The UV pair the base material's colour chains read at each ray's closest hit, after any
+        PositionalUVMaterial above the material (include/jsrt.h jsrt_material_uv): (uv n x 2 f32, has_uv n i32);
+        has_uv 0 = a miss, or a hit whose material_data has no UV (the pair is NaN)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = len(rays)
+        uv = np.empty((n, 2), np.float32)
+        has = np.empty(n, np.int32)
+        check(_native.posuv_api().jsrt_material_uv(self._h, rays.ctypes.data, n, uv.ctypes.data, has.ctypes.data),
+              "jsrt_material_uv")
+        return uv, has
+
     def sdf_distance(self, obj, points):
         """SDF.distance of SDFGeometry primitive `obj` (OBJS index) at local points (include/jsrt.h)."""
         points = np.ascontiguousarray(points, np.float32).reshape(-1, 4)
