@@ -158,6 +158,26 @@ int jsrt_finish_accum(const float *d_accum, int64_t n, int32_t kind, int32_t pas
 int jsrt_cast(jsrt_scene *scene, const float *rays, size_t n, double min_dist, double max_dist,
               int32_t intersect_transparent, double *out_dist, int32_t *out_object);
 
+/* The same rays through one of the other casts the render kernels run (known-answer tests; jsrt_cast runs the
+ * closest-hit cast of the extend kernel).  Arguments and outputs as jsrt_cast, except:
+ *   JSRT_CAST_ANY             the shadow kernels' any-hit cast, one lane per ray: the first accepted hit (any
+ *                             hit in (min_dist, max_dist), not the closest), -1 / +Infinity for none;
+ *   JSRT_CAST_ANY_MASKED      JSRT_CAST_ANY under the wave's shadow-root mask, taken as the shadow kernels take it:
+ *                             each lane's grid cell is that of its ray's origin, and a wave (64 consecutive rays)
+ *                             whose origins share a cell visits only the cell's roots.  The masks hold for segments
+ *                             from a hit point to a light sample point, min_dist 0.0001, max_dist 1, only;
+ *   JSRT_CAST_ANY_NODE        the node-per-lane shadow cast: groups of 4 consecutive rays that share an origin
+ *                             (n a multiple of 4, intersect_transparent 0); out_object -2 and out_dist NaN
+ *                             for a shadowed ray (no distance is computed), -1 / +Infinity otherwise;
+ *   JSRT_CAST_PERSISTENT      the SDF scenes' persistent closest-hit march: jsrt_cast's answers;
+ *   JSRT_CAST_PERSISTENT_ANY  the SDF scenes' persistent shadow march: as JSRT_CAST_ANY.
+ * Returns -2 without launching when the scene's kernel profile has no such path (ANY_NODE: scenes whose roots
+ * are all Primitives, none an SDF; PERSISTENT*: SDF scenes whose roots are all Primitives; ANY_MASKED: scenes with a
+ * shadow grid, i.e. bounded objects and lights and at most 64 top-level objects). */
+enum { JSRT_CAST_ANY = 1, JSRT_CAST_ANY_MASKED = 2, JSRT_CAST_ANY_NODE = 3, JSRT_CAST_PERSISTENT = 4, JSRT_CAST_PERSISTENT_ANY = 5 };
+int jsrt_cast_path(jsrt_scene *scene, const float *rays, size_t n, double min_dist, double max_dist,
+                   int32_t intersect_transparent, int32_t path, double *out_dist, int32_t *out_object);
+
 /* World.color(ray, 1) up to Material.color (world.js:31-41, 125-137) of n rays (as jsrt_cast): the
  * closest hit of World.cast(ray, 0) -- out_dist, out_object as jsrt_cast -- and the material_data the
  * hit Primitive hands to its material: normal (n x 4 f32: inv_transform.transposed().times(n).to4(0)

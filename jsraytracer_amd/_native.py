@@ -50,7 +50,7 @@ PROGRESS_EX_FN = ctypes.CFUNCTYPE(ctypes.c_int32, ctypes.c_int32, ctypes.c_doubl
 RC_ABORTED = -4  # jsrt_render_device_progress_ex: the callback asked to stop the frame
 
 # exported symbols of include/jsrt.h (checked by tests/test_capi_symbols.py)
-EXPORTS = ["jsrt_scene_create", "jsrt_scene_destroy", "jsrt_render", "jsrt_render_device", "jsrt_cast",
+EXPORTS = ["jsrt_scene_create", "jsrt_scene_destroy", "jsrt_render", "jsrt_render_device", "jsrt_cast", "jsrt_cast_path",
            "jsrt_material_data", "jsrt_material_uv", "jsrt_sdf_distance", "jsrt_material_color", "jsrt_owned_columns", "jsrt_last_error", "jsrt_abi_version",
            "jsrt_device_count", "jsrt_build_id", "jsrt_render_device_progress", "jsrt_render_device_progress_ex",
            "jsrt_render_device_accum", "jsrt_finish_accum", "jsrt_sdf_forms", "jsrt_scene_sdf_forms"]
@@ -140,6 +140,9 @@ def lib():
     L.jsrt_cast.restype = ctypes.c_int
     L.jsrt_cast.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_double,
                             ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+    L.jsrt_cast_path.restype = ctypes.c_int
+    L.jsrt_cast_path.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_double,
+                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     L.jsrt_material_data.restype = ctypes.c_int
     L.jsrt_material_data.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 7
     L.jsrt_sdf_distance.restype = ctypes.c_int

@@ -589,6 +589,35 @@ hipError_t cast_rays(const DScene &S, const float *d_rays, uint32_t n, double mi
     return hipGetLastError();
 }
 
+#define JSRT_CASTPATH_EXTERN(PFV) \
+    extern template bool cast_path_pf<PFV>(const DScene &, int, const float *, uint32_t, double, double, int, uint32_t *, \
+                                           double *, int32_t *, hipStream_t);
+JSRT_CASTPATH_EXTERN(PF_ANALYTIC)
+JSRT_CASTPATH_EXTERN(PF_MESH)
+JSRT_CASTPATH_EXTERN(PF_SDF)
+JSRT_CASTPATH_EXTERN(PF_ALL)
+#undef JSRT_CASTPATH_EXTERN
+
+hipError_t cast_rays_path(const DScene &S, int path, const float *d_rays, uint32_t n, double min_dist, double max_dist,
+                          bool transparent, uint32_t *d_ctr, double *d_t, int32_t *d_prim, hipStream_t st, bool *have) {
+    *have = true;
+    if (n == 0) return hipSuccess;
+    const int tr = transparent ? 1 : 0;
+    // the persistent march serves SDF scenes whose roots are all Primitives (render_frame's `persist`), the
+    // node-per-lane shadow cast flat scenes (every root a Primitive, no SDF: cast_path_pf)
+    if ((path == CAST_PATH_PERSISTENT || path == CAST_PATH_PERSISTENT_ANY || path == CAST_PATH_ANY_NODE) && !S.all_roots_prims) {
+        *have = false;
+        return hipSuccess;
+    }
+    switch (S.profile) {
+    case PF_ANALYTIC: *have = cast_path_pf<PF_ANALYTIC>(S, path, d_rays, n, min_dist, max_dist, tr, d_ctr, d_t, d_prim, st); break;
+    case PF_MESH: *have = cast_path_pf<PF_MESH>(S, path, d_rays, n, min_dist, max_dist, tr, d_ctr, d_t, d_prim, st); break;
+    case PF_SDF: *have = cast_path_pf<PF_SDF>(S, path, d_rays, n, min_dist, max_dist, tr, d_ctr, d_t, d_prim, st); break;
+    default: *have = cast_path_pf<PF_ALL>(S, path, d_rays, n, min_dist, max_dist, tr, d_ctr, d_t, d_prim, st); break;
+    }
+    return hipGetLastError();
+}
+
 namespace {
 template <bool CHAIN>
 void run_batch_pf(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t st, KernelTimes *kt,

@@ -195,6 +195,12 @@ hipError_t finish_accum(const float *accum, size_t n, int kind, int passes, uint
 
 // World.cast (world.js:28-30) of n rays (device buffers: n x 6 f32 rays, origin w = 1, direction
 // w = 0): closest-hit distance and DPrim index (-1: none).  The jsrt_cast entry (known-answer tests).
+enum : int { CAST_PATH_ANY = 1, CAST_PATH_ANY_MASKED = 2, CAST_PATH_ANY_NODE = 3, CAST_PATH_PERSISTENT = 4, CAST_PATH_PERSISTENT_ANY = 5 };
+// One of the render's other casts over n rays (jsrt_cast_path, include/jsrt.h): *have = false when the scene's
+// kernel profile has no such path (nothing is launched).  d_ctr: one zeroed uint32_t (the persistent paths).
+hipError_t cast_rays_path(const DScene &S, int path, const float *d_rays, uint32_t n, double min_dist, double max_dist,
+                          bool transparent, uint32_t *d_ctr, double *d_t, int32_t *d_prim, hipStream_t st, bool *have);
+
 hipError_t cast_rays(const DScene &S, const float *d_rays, uint32_t n, double min_dist, double max_dist, bool transparent,
                      double *d_t, int32_t *d_prim, hipStream_t st);
 

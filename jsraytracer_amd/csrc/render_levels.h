@@ -1377,6 +1377,115 @@ void cast_rays_pf(const DScene &S, const float *rays, uint32_t n, double minD, d
     hipLaunchKernelGGL((k_cast_rays<PF>), dim3(grid_ub(n)), dim3(256), lds, st, S, rays, n, minD, maxD, transp, t, prim);
 }
 
+// The casts the render's shadow and SDF kernels run, over a batch of independent rays (jsrt_cast_path, known-answer
+// tests): out_t / out_prim take the accepted hit (an any-hit cast: the first accepted one, -1 for none).
+// CAST_PATH_ANY: k_shadow's world_cast<PF, true>, one lane per ray, every root in the mask.
+template <int PF>
+__global__ __launch_bounds__(256) void k_cast_any(DScene S, const float *rays, uint32_t n, double minD, double maxD,
+                                                  int transp, double *out_t, int32_t *out_prim) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float *r = rays + 6 * (size_t)i;
+    const F3 o = f3(r[0], r[1], r[2]), d = f3(r[3], r[4], r[5]);
+    const Hit h = world_cast<PF, true>(S, o, d, minD, maxD, transp != 0, ~0ull);
+    out_t[i] = h.t;
+    out_prim[i] = h.prim;
+}
+// CAST_PATH_ANY_MASKED: the same with the wave's shadow-root mask, taken as k_shadow takes it: the lane's cell is
+// grid_cell of its origin (k_extend's bucket of the hit point the shadow ray leaves from), and wave_root_mask
+// gives the cell's mask when the wave's 64 origins share it (every root otherwise).  Valid for segments from a
+// hit point to a light sample point only (scene_load.cpp shadow_grid).  No lane leaves before the ballots.
+template <int PF>
+__global__ __launch_bounds__(256) void k_cast_any_masked(DScene S, const float *rays, uint32_t n, double minD, double maxD,
+                                                         int transp, double *out_t, int32_t *out_prim) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const bool in = i < n;
+    const float *r = rays + 6 * (size_t)(in ? i : 0u);
+    const F3 o = f3(r[0], r[1], r[2]), d = f3(r[3], r[4], r[5]);
+    const uint64_t mask = wave_root_mask(S, (uint32_t)grid_cell(S, o), in);
+    if (!in) return;
+    const Hit h = world_cast<PF, true>(S, o, d, minD, maxD, transp != 0, mask);
+    out_t[i] = h.t;
+    out_prim[i] = h.prim;
+}
+// CAST_PATH_ANY_NODE: k_shadow_node's world_any_node<PF, 4>, one lane per group of 4 consecutive rays that share
+// the first one's origin (n = 4 x groups; shadow casters only).  No distance comes back: out_t is NaN for a
+// shadowed ray, +Infinity otherwise, out_prim -2 / -1.  The flat profile only, as k_shadow_node.
+template <int PF>
+__global__ __launch_bounds__(256) void k_cast_any_node(DScene S, const float *rays, uint32_t groups, double minD,
+                                                       double maxD, double *out_t, int32_t *out_prim) {
+    if constexpr (PF == PF_ANALYTIC) {
+        const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+        if (g >= groups) return;
+        const float *r = rays + 24 * (size_t)g;
+        const F3 o = f3(r[0], r[1], r[2]);
+        F3 d[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) d[s] = f3(r[6 * s + 3], r[6 * s + 4], r[6 * s + 5]);
+        const uint32_t live = world_any_node<PF, 4>(S, o, d, 0xFu, minD, maxD, ~0ull);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const bool lit = (live >> s) & 1u;
+            out_t[4 * (size_t)g + s] = lit ? DINF : (double)__builtin_nanf("");
+            out_prim[4 * (size_t)g + s] = lit ? -1 : -2;
+        }
+    }
+}
+// CAST_PATH_PERSISTENT / _ANY: k_extend_q's / k_shadow_cast's persistent_cast over the ray array (ray j = job j)
+struct RayArraySrc {
+    const float *rays;
+    double *t;
+    int32_t *prim;
+    __device__ __forceinline__ bool load(uint32_t j, F3 &o, F3 &d) const {
+        const float *r = rays + 6 * (size_t)j;
+        o = f3(r[0], r[1], r[2]);
+        d = f3(r[3], r[4], r[5]);
+        return true;
+    }
+    __device__ __forceinline__ void store(uint32_t j, const Hit &h) const {
+        t[j] = h.t;
+        prim[j] = h.prim;
+    }
+};
+template <int PF, bool ANY, bool FO>
+__global__ __launch_bounds__(256, JSRT_MARCH_OCC) void k_cast_persistent(DScene S, const float *rays, uint32_t n,
+                                                                         double minD, double maxD, int transp,
+                                                                         uint32_t *ctr, double *out_t, int32_t *out_prim) {
+    if constexpr ((PF & PF_SDF) != 0) {
+        RayArraySrc src{rays, out_t, out_prim};
+        persistent_cast<PF, ANY, FO>(S, ctr, n, minD, maxD, transp != 0, src);
+    }
+}
+// Launches one path; false: the profile does not have it (nothing launched).  ctr: one zeroed work counter.
+template <int PF>
+bool cast_path_pf(const DScene &S, int path, const float *rays, uint32_t n, double minD, double maxD, int transp,
+                  uint32_t *ctr, double *t, int32_t *prim, hipStream_t st) {
+    const size_t lds = (PF & (PF_BVH | PF_AGG)) ? bvh_lds_bytes(S, 256) : 0;
+    if (path == CAST_PATH_ANY) {
+        hipLaunchKernelGGL((k_cast_any<PF>), dim3(grid_ub(n)), dim3(256), lds, st, S, rays, n, minD, maxD, transp, t, prim);
+        return true;
+    }
+    if (path == CAST_PATH_ANY_MASKED) {
+        if (!(S.grid_cells > 0 && S.grid_masked)) return false;  // the render takes no mask either (W.bucket_grid)
+        hipLaunchKernelGGL((k_cast_any_masked<PF>), dim3(grid_ub(n)), dim3(256), lds, st, S, rays, n, minD, maxD, transp, t, prim);
+        return true;
+    }
+    if (path == CAST_PATH_ANY_NODE) {
+        if (PF != PF_ANALYTIC) return false;  // the profile whose renders run k_shadow_node
+        hipLaunchKernelGGL((k_cast_any_node<PF>), dim3(grid_ub(n / 4)), dim3(256), 0, st, S, rays, n / 4, minD, maxD, t, prim);
+        return true;
+    }
+    if (!(PF & PF_SDF)) return false;
+    const bool any = path == CAST_PATH_PERSISTENT_ANY;
+    auto launch = [&](auto k) {
+        hipLaunchKernelGGL(k, dim3(persistent_grid((const void *)k, n)), dim3(256), 0, st, S, rays, n, minD, maxD, transp,
+                           ctr, t, prim);
+    };
+    if (S.sdf_all_forms) any ? launch(k_cast_persistent<PF, true, true>) : launch(k_cast_persistent<PF, false, true>);
+    else any ? launch(k_cast_persistent<PF, true, false>) : launch(k_cast_persistent<PF, false, false>);
+    return true;
+}
+
 // World.color(ray, 1) up to Material.color for a batch of rays (jsrt_material_data, the material-data
 // known answers): the closest hit of World.cast(ray, 0) (world.js:34) and the hit's surface_data.
 // Absent fields are NaN; uv[2] is always NaN (the kernels read u, v only).

@@ -24,6 +24,8 @@ template void run_batch<JSRT_PF, false>(const DScene &, const RenderArgs &, cons
 #if JSRT_PART < 0 || JSRT_PART == 2
 template void cast_rays_pf<JSRT_PF>(const DScene &, const float *, uint32_t, double, double, int, double *, int32_t *,
                                    hipStream_t);
+template bool cast_path_pf<JSRT_PF>(const DScene &, int, const float *, uint32_t, double, double, int, uint32_t *, double *,
+                                   int32_t *, hipStream_t);
 template void material_data_pf<JSRT_PF>(const DScene &, const float *, uint32_t, double *, int32_t *, float *, float *,
                                         float *, float *, float *, hipStream_t);
 template void material_uv_pf<JSRT_PF>(const DScene &, const float *, uint32_t, float *, int32_t *, hipStream_t);

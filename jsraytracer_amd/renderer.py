@@ -77,6 +77,23 @@ class Scene:
                                       t.ctypes.data, obj.ctypes.data), "jsrt_cast")
         return t, obj
 
+    CAST_PATHS = {"any": 1, "any_masked": 2, "any_node": 3, "persistent": 4, "persistent_any": 5}
+
+    def cast_path(self, rays, min_dist=0.0, max_dist=float("inf"), intersect_transparent=True, path="any"):
+        """The rays of cast() through another of the render's casts (include/jsrt.h jsrt_cast_path): "any" (the
+        shadow kernels' any-hit cast), "any_masked" (the same under the wave's shadow-root mask: segments from hit
+        points to light sample points, a wave's 64 origins in one grid cell), "any_node" (groups of 4 rays sharing an origin; a shadowed ray reads
+        obj -2, t NaN), "persistent" / "persistent_any" (the SDF marches).  (distance, OBJS index) as cast();
+        JsrtError when the scene's kernel profile has no such path."""
+        import numpy as np
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = len(rays)
+        t = np.empty(n, np.float64)
+        obj = np.empty(n, np.int32)
+        check(_native.lib().jsrt_cast_path(self._h, rays.ctypes.data, n, min_dist, max_dist, int(bool(intersect_transparent)),
+                                           self.CAST_PATHS[path], t.ctypes.data, obj.ctypes.data), "jsrt_cast_path")
+        return t, obj
+
     def material_data(self, rays):
         """World.color(ray, 1) up to Material.color (include/jsrt.h jsrt_material_data): dict of t, obj,
         normal (n x 4), position (n x 4), uv (n x 3), bary (n x 3), basecolor (n x 3); NaN = absent."""

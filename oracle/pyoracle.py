@@ -210,22 +210,47 @@ def golden_material_scenes(sub=None):
     return sorted(f[:-len(".json.gz")] for f in os.listdir(_golden(sub, "material")) if f.endswith(".json.gz"))
 
 
-def golden_casts(name, sub=None):
+def golden_casts(name, sub=None, kind="casts"):
     """World.cast known answers computed by the reference (oracle/refharness/make_cast_kats.js):
-    {"blob_sha256", "sets": [{name, minD, maxD, transp, rays (n x 6 f32), t (f64), obj (i32)}]}."""
+    {"blob_sha256", "sets": [{name, minD, maxD, transp, rays (n x 6 f32), t (f64), obj (i32)}]}.
+    kind="casts_edge" (make_edge_cast_kats.js): a set may share another's rays ("rays_of", resolved here), carry
+    per-ray ranges (minD / maxD are then f64 arrays of n) and "aim" (i32, the triangle a ray was aimed at).
+    kind="casts_light" (make_light_cast_kats.js): one set, "to_light", in groups of "group" rays sharing an origin."""
     import base64
-    with gzip.open(_golden(sub, "casts", name + ".json.gz"), "rt") as f:
+    with gzip.open(_golden(sub, kind, name + ".json.gz"), "rt") as f:
         d = json.load(f)
+    by_name = {}
     for s in d["sets"]:
-        s["maxD"] = float(s["maxD"])
-        s["rays"] = np.frombuffer(base64.b64decode(s["rays"]), np.float32).reshape(-1, 6)
+        s["rays"] = (np.frombuffer(base64.b64decode(s["rays"]), np.float32).reshape(-1, 6) if "rays" in s
+                     else by_name[s["rays_of"]]["rays"])
+        for k in ("minD", "maxD"):
+            s[k] = np.frombuffer(base64.b64decode(s.pop(k + "_each")), np.float64) if k + "_each" in s else float(s[k])
         s["t"] = np.frombuffer(base64.b64decode(s["t"]), np.float64)
         s["obj"] = np.frombuffer(base64.b64decode(s["obj"]), np.int32)
+        if "aim" in s:
+            s["aim"] = np.frombuffer(base64.b64decode(s["aim"]), np.int32)
+        by_name[s["name"]] = s
     return d
 
 
-def golden_cast_scenes(sub=None):
-    return sorted(f[:-len(".json.gz")] for f in os.listdir(_golden(sub, "casts")) if f.endswith(".json.gz"))
+def golden_cast_scenes(sub=None, kind="casts"):
+    return sorted(f[:-len(".json.gz")] for f in os.listdir(_golden(sub, kind)) if f.endswith(".json.gz"))
+
+
+def cast_set(cast_fn, s):
+    """A known-answer set `s` through cast_fn(rays, minD, maxD, transp) -> (t, obj): one call, or one call per
+    distinct range where the set carries per-ray ranges.  (A lim_tie set is 180 rays with a range each, so 180
+    one-ray calls: through the GPU entries that is 180 launches with their allocations, a known cost of well
+    under a second per set that keeps the entries' signature to one range per call.)"""
+    if np.ndim(s["minD"]) == 0 and np.ndim(s["maxD"]) == 0:
+        return cast_fn(s["rays"], s["minD"], s["maxD"], s["transp"])
+    n = len(s["rays"])
+    lo, hi = np.broadcast_to(s["minD"], n), np.broadcast_to(s["maxD"], n)
+    t, obj = np.empty(n, np.float64), np.empty(n, np.int32)
+    for a, b in sorted(set(zip(lo.tolist(), hi.tolist()))):
+        m = (lo == a) & (hi == b)
+        t[m], obj[m] = cast_fn(s["rays"][m], a, b, s["transp"])
+    return t, obj
 
 
 # ---- mesh fixtures (oracle/refharness/regen_mesh_fixtures.sh): skeleton + OBJ + MTL per scene ----
