@@ -38,7 +38,7 @@ function loadReference() {
 // configureTest(callback) produces (tests/<name>/test.mjs).
 // A name one of this project's own scene modules defines (LOCAL_SCENES: modules beside this file exporting
 // `scenes`, name -> function returning that same object) resolves there instead.
-const LOCAL_SCENES = ["./zoo_scenes"];
+const LOCAL_SCENES = ["./zoo_scenes", "./shade_zoo_scenes"];
 
 function loadScene(name) {
     loadReference();
