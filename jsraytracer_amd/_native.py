@@ -61,6 +61,13 @@ MESH_EXPORTS = ["jsrt_blob_attach_obj", "jsrt_blob_attach_obj_mtl", "jsrt_blob_a
 JSON_EXPORTS = ["jsrt_blob_from_json"]
 # exported symbols of include/jsrt_texture.h (an MCOL record turned into a texture; host-only)
 TEXTURE_EXPORTS = ["jsrt_blob_set_texture"]
+# exported symbols of include/jsrt_color.h (World.color of caller-supplied rays, the rays of a frame)
+COLOR_EXPORTS = ["jsrt_color", "jsrt_color_device", "jsrt_camera_rays"]
+
+
+class ColorParams(ctypes.Structure):  # jsrt_color_params
+    _fields_ = [("max_depth", ctypes.c_int32), ("seed", ctypes.c_uint32), ("sample0", ctypes.c_uint32),
+                ("spp", ctypes.c_int32), ("max_paths", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
 class MeshOptions(ctypes.Structure):
@@ -199,6 +206,23 @@ def posuv_api():
         raise JsrtError(f"{LIB_PATH} has no jsrt_material_uv: rebuild it")
     L.jsrt_material_uv.restype = ctypes.c_int
     L.jsrt_material_uv.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    return L
+
+
+def color_api():
+    """The library with the jsrt_color.h entry points bound (JsrtError if it lacks them); bound where they are
+    called, as the texture entry points are."""
+    L = lib()
+    if not all(hasattr(L, n) for n in COLOR_EXPORTS):
+        raise JsrtError(f"{LIB_PATH} has no jsrt_color entry points: rebuild it")
+    L.jsrt_color.restype = ctypes.c_int
+    L.jsrt_color.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                             ctypes.POINTER(ColorParams), ctypes.c_void_p, ctypes.POINTER(Stats)]
+    L.jsrt_color_device.restype = ctypes.c_int
+    L.jsrt_color_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                    ctypes.POINTER(ColorParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Stats)]
+    L.jsrt_camera_rays.restype = ctypes.c_int
+    L.jsrt_camera_rays.argtypes = [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_uint32, ctypes.c_void_p]
     return L
 
 

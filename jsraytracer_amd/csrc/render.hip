@@ -67,6 +67,30 @@ __global__ __launch_bounds__(256) void k_gen(DScene S, RenderArgs A, WArgs W) {
     W.prim[q] = -1;
 }
 
+// The caller's rays in the camera's place (color_frame): path q of the batch is ray W.p0 + q / nb, sample W.s0 + q % nb:
+// a ray's samples side by side, then the next ray's (the order k_gen calls pixel-major; at one sample per ray,
+// neighbouring lanes shade neighbouring rays).  W.pixel_major is deliberately not read, here or in k_store_colors: it
+// orders a frame's pixels for k_accum, and a ray batch has one order.  Keyed by (seed, the ray's key, sample).  The ray opens
+// the root World.color frame, address mix32(0, 1): the pre-root frame's draws (jitter, DOF) belong to a camera.
+// Level counts as k_gen writes them; A.max_depth >= 1 (color_frame answers World.color(ray, 0) itself).
+__global__ __launch_bounds__(256) void k_gen_rays(RenderArgs A, WArgs W, RayFeed F) {
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+    if ((!W.chain || W.hybrid) && q < LVL_UNDER) W.lvl[q] = q == 0 ? W.npaths : 0u;
+    if (q >= W.npaths) return;
+    const uint32_t nb = W.npaths / W.npix;
+    const uint32_t i = W.p0 + q / nb, smp = F.sample0 + W.s0 + q % nb;
+    if (!W.chain) {
+        W.path[q] = q;
+        W.parent[q] = NO_PARENT;
+    }
+    const float *r = F.rays + 6 * (size_t)i;
+    W.ox[q] = r[0]; W.oy[q] = r[1]; W.oz[q] = r[2];
+    W.dx[q] = r[3]; W.dy[q] = r[4]; W.dz[q] = r[5];
+    W.addr[q] = mix32(0u, 1u);
+    W.key[q] = mix32(mix32(A.seed, F.keys ? F.keys[i] : i), smp);
+    W.prim[q] = -1;
+}
+
 // tree schedule: surface + children, bottom-up into the parent's child slot (materials.js:277-330)
 __global__ __launch_bounds__(256) void k_reduce(WArgs W, int L) {
     const LevelRange R = level_range(W, L);
@@ -138,8 +162,26 @@ __global__ __launch_bounds__(256) void k_accum(RenderArgs A, WArgs W) {
     A.accum[4 * oi + 2] = acc.z;
 }
 
-// chain schedule: per pixel, its samples in order; each path's colour is resolved bottom-up over
-// its levels (surface + child contribution; a last-level child is black without a cast)
+// chain schedule: path q's colour, resolved bottom-up over its levels (surface + child contribution; a
+// last-level child is black without a cast)
+__device__ __forceinline__ F3 resolve_path(const RenderArgs &A, const WArgs &W, uint32_t q) {
+    F3 v = f3(0, 0, 0);  // World.color(ray, 0) = black
+    for (int L = A.max_depth - 1; L >= 0; --L) {
+        const uint32_t i = (uint32_t)L * W.cap + q;
+        const float4 nd = W.node[i];
+        const uint32_t info = f2u(nd.w);
+        if (info & INFO_MISS) {
+            v = f3(nd.x, nd.y, nd.z);
+        } else if (info & INFO_HIT) {
+            F3 col = f3(nd.x, nd.y, nd.z);
+            if ((info >> INFO_NCHILD_SHIFT) & 3) col = add_child(W, i, 0, col, L == A.max_depth - 1 ? f3(0, 0, 0) : v, info);
+            v = col;
+        }
+    }
+    return v;
+}
+
+// chain schedule: per pixel, its samples in order
 __global__ __launch_bounds__(256) void k_resolve(RenderArgs A, WArgs W) {
     const uint32_t pl = blockIdx.x * 256 + threadIdx.x;
     if (pl >= W.npix) return;
@@ -150,20 +192,7 @@ __global__ __launch_bounds__(256) void k_resolve(RenderArgs A, WArgs W) {
     const uint32_t nsb = W.npaths / W.npix;
     for (uint32_t sl = 0; sl < nsb; ++sl) {
         const uint32_t q = W.pixel_major ? pl * nsb + sl : sl * W.npix + pl;
-        F3 v = f3(0, 0, 0);  // World.color(ray, 0) = black
-        for (int L = A.max_depth - 1; L >= 0; --L) {
-            const uint32_t i = (uint32_t)L * W.cap + q;
-            const float4 nd = W.node[i];
-            const uint32_t info = f2u(nd.w);
-            if (info & INFO_MISS) {
-                v = f3(nd.x, nd.y, nd.z);
-            } else if (info & INFO_HIT) {
-                F3 col = f3(nd.x, nd.y, nd.z);
-                if ((info >> INFO_NCHILD_SHIFT) & 3) col = add_child(W, i, 0, col, L == A.max_depth - 1 ? f3(0, 0, 0) : v, info);
-                v = col;
-            }
-        }
-        acc = accumulate(A, acc, v);
+        acc = accumulate(A, acc, resolve_path(A, W, q));
     }
     A.accum[4 * oi] = acc.x;
     A.accum[4 * oi + 1] = acc.y;
@@ -252,6 +281,43 @@ __global__ __launch_bounds__(256) void k_resolve_paths(RenderArgs A, WArgs W) {
     W.root[3 * q] = v.x;
     W.root[3 * q + 1] = v.y;
     W.root[3 * q + 2] = v.z;
+}
+
+// The colours of a batch of the caller's rays (k_gen_rays): path q's resolved colour to out[3 * (ray * spp + sample)],
+// as it is -- no accumulation, no 1 / passes, no setColor.  Chain schedule: resolved here, as k_resolve does for one
+// sample; tree and hybrid chain: from root (k_reduce / k_resolve_paths).  A poisoned batch writes nothing: the
+// host redoes it, as it redoes a frame.
+__global__ __launch_bounds__(256) void k_store_colors(RenderArgs A, WArgs W, RayFeed F) {
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= W.npaths || W.lvl[LVL_FLAG]) return;
+    const uint32_t nb = W.npaths / W.npix;
+    const F3 v = (W.chain && !W.hybrid) ? resolve_path(A, W, q) : f3(W.root[3 * q], W.root[3 * q + 1], W.root[3 * q + 2]);
+    float *dst = F.out + 3 * ((size_t)(W.p0 + q / nb) * F.spp + W.s0 + q % nb);
+    dst[0] = v.x;
+    dst[1] = v.y;
+    dst[2] = v.z;
+}
+
+// k_gen's ray computation with the ray as the output (Camera.getRayForPixel as a batch): pixel p = py * W + px of
+// A's W x H, sample index `sample`; the jitter of the sampling renderers (renderers.js:95-96) and camera_ray's DOF
+// draws come from the pre-root frame of key (seed, pixel, sample), as in k_gen
+__global__ __launch_bounds__(256) void k_camera_rays(DScene S, RenderArgs A, uint32_t sample, float *out) {
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= (uint32_t)A.W * (uint32_t)A.H) return;
+    const int py = (int)(p / (uint32_t)A.W), px = (int)(p % (uint32_t)A.W);
+    Rng pre{mix32(mix32(A.seed, p), sample), 0u, 0u};
+    double x = 2 * ((double)px / A.W) - 1, y = -2 * ((double)py / A.H) + 1;  // renderers.js:22-25
+    if (A.kind != JSRT_RENDERER_SIMPLE) {
+        const double jx = x + (2.0 / A.W) * (pre.next() - 0.5);
+        const double jy = y + (2.0 / A.H) * (pre.next() - 0.5);
+        x = jx;
+        y = jy;
+    }
+    F3 o, d;
+    camera_ray(S.cam, x, y, pre, o, d);
+    float *r = out + 6 * (size_t)p;
+    r[0] = o.x; r[1] = o.y; r[2] = o.z;
+    r[3] = d.x; r[4] = d.y; r[5] = d.z;
 }
 
 __global__ __launch_bounds__(256) void k_final(RenderArgs A, int32_t passes) {
@@ -631,11 +697,14 @@ void run_batch_pf(const DScene &S, const RenderArgs &A, const WArgs &W, hipStrea
 }
 }  // namespace
 
-hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront &wf, hipStream_t st, KernelTimes *kt,
-                        size_t max_paths, const std::function<bool(int, double, bool)> &progress,
-                        const std::function<bool()> &due) {
-    if (!A.accum) return hipErrorInvalidValue;
-    const uint32_t npix_total = (uint32_t)A.patches * 64u;
+// A frame's batches: the camera's paths of the owned pixels into A.accum (render_frame), or -- feed -- World.color of
+// the caller's rays into feed->out (color_frame), where a "pixel" of the plan is a ray and nothing of the pixel order
+// (pixel_of, tiles, column ownership) is involved.  One plan, level loop, pools, streams and redo logic for both.
+static hipError_t run_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront &wf, hipStream_t st, KernelTimes *kt,
+                            size_t max_paths, const std::function<bool(int, double, bool)> &progress,
+                            const std::function<bool()> &due, const RayFeed *feed) {
+    if (!feed && !A.accum) return hipErrorInvalidValue;
+    const uint32_t npix_total = feed ? feed->n : (uint32_t)A.patches * 64u;
     if (npix_total == 0) {  // a rank that owns no column (a multi-GPU frame narrower than its column blocks):
         // nothing to trace, but an Incremental frame's passes are still reported, so that the rank's callbacks
         // keep step with its peers' (tiles.render_progressive runs one collective per reported pass)
@@ -794,7 +863,7 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
         };
         WArgs W = settings(wf.args);
         WArgs W2 = dual ? settings(wf.twin->args) : W;  // the twin pool: the same settings over its own buffers
-        if ((e = hipMemsetAsync(A.accum, 0, (size_t)A.ncols * A.H * 4 * sizeof(float), st)) != hipSuccess) break;
+        if (!feed && (e = hipMemsetAsync(A.accum, 0, (size_t)A.ncols * A.H * 4 * sizeof(float), st)) != hipSuccess) break;
         if ((e = hipMemsetAsync(W.lvl + LVL_UNDER, 0, 2 * sizeof(uint32_t), st)) != hipSuccess) break;  // frame flags
         if ((e = hipMemsetAsync(W.fixctr, 0, sizeof(uint32_t), st)) != hipSuccess) break;
         if (dual && (e = hipMemsetAsync(W2.fixctr, 0, sizeof(uint32_t), st)) != hipSuccess) break;
@@ -855,6 +924,7 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
                 Wb.cap = hybrid ? (uint32_t)cap : Wb.npaths;
                 const std::vector<size_t> bound = learned ? bounds(Wb.npaths) : std::vector<size_t>();
                 BatchSync sync;
+                sync.feed = feed;
                 if (dual) {
                     sync.wait = bi > 0 ? ev_acc[(bi - 1) & 1] : nullptr;
                     sync.done = ev_acc[bi & 1];
@@ -959,6 +1029,35 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
     if (ev) kt->ev[KT_FINAL].begin(st);
     hipLaunchKernelGGL(k_final, dim3(grid((size_t)A.ncols * A.H)), dim3(256), 0, st, A, (int32_t)A.spp);
     if (ev) kt->ev[KT_FINAL].end(st);
+    return hipGetLastError();
+}
+
+hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront &wf, hipStream_t st, KernelTimes *kt,
+                        size_t max_paths, const std::function<bool(int, double, bool)> &progress,
+                        const std::function<bool()> &due) {
+    return run_frame(S, A, ns, wf, st, kt, max_paths, progress, due, nullptr);
+}
+
+hipError_t color_frame(const DScene &S, const RenderArgs &A, const RayFeed &F, int ns, Wavefront &wf, hipStream_t st,
+                       KernelTimes *kt, size_t max_paths) {
+    if (F.n == 0 || F.spp == 0) return hipSuccess;
+    if (!F.rays || !F.out || A.max_depth < 0 || A.max_depth > MAX_TREE_DEPTH) return hipErrorInvalidValue;
+    if (A.max_depth == 0)  // World.color(ray, 0) = black (world.js:32): nothing is traced
+        return hipMemsetAsync(F.out, 0, (size_t)F.n * F.spp * 3 * sizeof(float), st);
+    RenderArgs Ar{};  // what the plan and the kernels after the first read of a frame: the batch grid, depth and seed
+    Ar.max_depth = A.max_depth;
+    Ar.seed = A.seed;
+    Ar.spp = (int32_t)F.spp;
+    Ar.kind = JSRT_RENDERER_RANDOM;  // (no pass structure: nothing is reported)
+    Ar.patches = (int32_t)(((uint64_t)F.n + 63) / 64);  // the plan's pixel count, in whole 64s
+    return run_frame(S, Ar, ns, wf, st, kt, max_paths, nullptr, nullptr, &F);
+}
+
+hipError_t camera_rays(const DScene &S, const RenderArgs &A, uint32_t sample, float *d_rays, hipStream_t st) {
+    const size_t n = (size_t)A.W * A.H;
+    if (n == 0) return hipSuccess;
+    if (!d_rays || n > (size_t)UINT32_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_camera_rays, dim3(grid(n)), dim3(256), 0, st, S, A, sample, d_rays);
     return hipGetLastError();
 }
 

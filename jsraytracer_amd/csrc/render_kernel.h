@@ -109,15 +109,29 @@ struct WArgs {
     size_t sstride;           // entries of sray / scol (0: persistent casts not used)
 };
 
+// A batch of World.color calls on the caller's rays (color_frame, jsrt_color.h) instead of the camera's: where a
+// frame's batches take their level-0 rays from (k_gen_rays) and where their paths' colours go (k_store_colors).
+// A batch is rays [W.p0, W.p0 + W.npix) x samples [W.s0, W.s0 + npaths / npix), a ray's samples side by side
+// (W.pixel_major is not read).
+struct RayFeed {
+    const float *rays;     // n x 6 f32: origin xyz (w = 1), direction xyz (w = 0)
+    const uint32_t *keys;  // n: the "pixel" of a ray's RNG key (nullable: the ray's index)
+    float *out;            // n x spp x 3 f32: World.color of (ray, sample)
+    uint32_t n, spp, sample0;
+};
+
 // Accumulation order across the two batch streams (render_frame): the batch's k_accum / k_resolve waits
 // for `wait` (the previous batch's accumulation, on the other stream) and records `done` after itself.
 // aux (optional): the stream k_shadow runs on, so that level L's shadow samples overlap level L + 1's
 // closest-hit casts (they share no buffer); shade_done / shadow_done order k_shadow(L) after k_shade(L)
 // and k_shade(L + 1) -- which rewrites the hand-off -- after k_shadow(L).
+// feed (optional): the batch shades the caller's rays (RayFeed above): k_gen_rays in k_gen's place, k_store_colors
+// in the accumulation's.
 struct BatchSync {
     hipEvent_t wait = nullptr, done = nullptr;
     hipStream_t aux = nullptr;
     hipEvent_t shade_done = nullptr, shadow_done = nullptr;
+    const RayFeed *feed = nullptr;
 };
 
 struct Wavefront {  // owns the batch buffers (cached per scene)
@@ -181,6 +195,14 @@ struct KernelTimes {
 hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront &wf, hipStream_t st, KernelTimes *kt,
                         size_t max_paths, const std::function<bool(int, double, bool)> &progress,
                         const std::function<bool()> &due = nullptr);
+
+// World.color(ray, A.max_depth) of F.n rays x F.spp samples (device buffers) through the frame's batches, level
+// loop, pools, streams and redo logic: of A only max_depth (>= 1) and seed are read.
+hipError_t color_frame(const DScene &S, const RenderArgs &A, const RayFeed &F, int ns, Wavefront &wf, hipStream_t st,
+                       KernelTimes *kt, size_t max_paths);
+// The ray k_gen starts for every pixel py * W + px of A's W x H and sample index `sample` (jitter and DOF draws
+// from the pre-root frame of key (seed, pixel, sample)): W * H x 6 f32.
+hipError_t camera_rays(const DScene &S, const RenderArgs &A, uint32_t sample, float *d_rays, hipStream_t st);
 
 // Device bytes of the batch state per path of a batch (Wavefront::reserve for the schedule and pool
 // render_frame picks for this scene): caps the default batch size.

@@ -666,6 +666,9 @@ __global__ __launch_bounds__(256) void k_accum(RenderArgs A, WArgs W);
 __global__ __launch_bounds__(256) void k_resolve(RenderArgs A, WArgs W);
 __global__ __launch_bounds__(256) void k_resolve_side(RenderArgs A, WArgs W, int s);
 __global__ __launch_bounds__(256) void k_resolve_paths(RenderArgs A, WArgs W);
+// a batch of the caller's rays (RayFeed): k_gen's and k_accum / k_resolve's twins
+__global__ __launch_bounds__(256) void k_gen_rays(RenderArgs A, WArgs W, RayFeed F);
+__global__ __launch_bounds__(256) void k_store_colors(RenderArgs A, WArgs W, RayFeed F);
 
 // Grid of a persistent kernel: as many 256-thread blocks as the device keeps resident (occupancy x
 // CUs), never more than the work needs (render.hip).
@@ -1590,7 +1593,13 @@ void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t
     const bool Q = (PF & PF_SDF) && W.sstride != 0;
     if (Q) (void)hipMemsetAsync(W.qctr, 0, 64 * sizeof(uint32_t), st);
     if (W.bucket) (void)hipMemsetAsync(W.bkt, 0, (size_t)MAX_TREE_DEPTH * BKT_LEVEL * sizeof(uint32_t), st);
-    timed(KT_GEN, [&] { hipLaunchKernelGGL(k_gen, dim3(grid(W.npaths)), dim3(256), 0, st, S, A, W); });
+    const RayFeed *feed = sync ? sync->feed : nullptr;  // the caller's rays in the camera's place
+    timed(KT_GEN, [&] {
+        if (feed) hipLaunchKernelGGL(k_gen_rays, dim3(grid(W.npaths)), dim3(256), 0, st, A, W, *feed);
+        else hipLaunchKernelGGL(k_gen, dim3(grid(W.npaths)), dim3(256), 0, st, S, A, W);
+    });
+    // the batch's colours: into the frame's accumulator per pixel, or each path's own to the caller (k_store_colors)
+    auto store = [&] { hipLaunchKernelGGL(k_store_colors, dim3(grid(W.npaths)), dim3(256), 0, st, A, W, *feed); };
     std::vector<size_t> ubs;  // launch bound of each level's ray count
     const bool learned = !CHAIN || W.hybrid;  // launch bounds from the host (learned level counts)
     for (int L = 0; L < A.max_depth && (!learned || bound[L] > 0); ++L) {
@@ -1685,20 +1694,29 @@ void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t
             hipLaunchKernelGGL(k_resolve_paths, dim3(grid(W.npaths)), dim3(256), 0, st, A, W);
         });
         accum_wait();
-        timed(KT_ACCUM, [&] { hipLaunchKernelGGL(k_accum, dim3(grid(W.npix)), dim3(256), 0, st, A, W); });
+        timed(KT_ACCUM, [&] {
+            if (feed) store();
+            else hipLaunchKernelGGL(k_accum, dim3(grid(W.npix)), dim3(256), 0, st, A, W);
+        });
         accum_done();
         return;
     }
     if (CHAIN) {
         accum_wait();
-        timed(KT_RESOLVE, [&] { hipLaunchKernelGGL(k_resolve, dim3(grid(W.npix)), dim3(256), 0, st, A, W); });
+        timed(KT_RESOLVE, [&] {
+            if (feed) store();
+            else hipLaunchKernelGGL(k_resolve, dim3(grid(W.npix)), dim3(256), 0, st, A, W);
+        });
         accum_done();
         return;
     }
     for (int L = (int)ubs.size() - 1; L >= 0; --L)
         timed(KT_REDUCE, [&] { hipLaunchKernelGGL(k_reduce, dim3(grid_ub(ubs[L])), dim3(256), 0, st, W, L); });
     accum_wait();
-    timed(KT_ACCUM, [&] { hipLaunchKernelGGL(k_accum, dim3(grid(W.npix)), dim3(256), 0, st, A, W); });
+    timed(KT_ACCUM, [&] {
+        if (feed) store();
+        else hipLaunchKernelGGL(k_accum, dim3(grid(W.npix)), dim3(256), 0, st, A, W);
+    });
     accum_done();
 }
 

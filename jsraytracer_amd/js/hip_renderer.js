@@ -32,6 +32,16 @@ function addon() {
     return _addon;
 }
 
+// World.color of caller-supplied rays (include/jsrt_color.h): a module of its own beside jsrt_node.node, taking its
+// scene handles (jsrt_node_color.cpp)
+let _colorAddon = null;
+function colorAddon() {
+    if (_colorAddon) return _colorAddon;
+    addon();  // the ABI check, and the module whose scene handles this one takes
+    _colorAddon = require(process.env.JSRT_NODE_COLOR_ADDON || path.join(__dirname, "..", "_build", "jsrt_node_color.node"));
+    return _colorAddon;
+}
+
 /*
  * The device a worker renders on: worker i of the reference's launcher (src/raytrace_launcher.js:65-101,
  * which spawns N workers over one CPU) goes to GPU i % deviceCount, so N workers spread over a node's
@@ -117,6 +127,21 @@ class HipRenderer {
         const cb = (timelimit && callback) ? (pass, completion) => callback({ pass, completion }) : undefined;
         return addon().render(this.handle, p, img.imgdata.data, cb).then((st) => { this.stats = st; return img; });
     }
+    /*
+     * World.color (src/world.js:31-41) of the caller's rays, for a host with its own camera: rays is a Float32Array
+     * of n x 6 (origin xyz, direction xyz).  opts: {keys: Uint32Array (n; absent: the ray's index), sample0 = 0,
+     * samplesPerRay = 1, maxRecursionDepth, seed (default: the renderer's), maxPaths = 0}.  Sample s of ray i draws
+     * from the keyed Math.random at (seed, pixel = keys[i], sample = sample0 + s).  Resolves to a Float32Array of
+     * n x samplesPerRay x 3: the colours as World.color returns them, before any accumulation or setColor.  Runs
+     * as async work, like renderAsync.
+     */
+    color(rays, opts = {}) {
+        if (!this.handle) throw "HipRenderer: the scene was destroyed";
+        const p = { maxRecursionDepth: opts.maxRecursionDepth !== undefined ? opts.maxRecursionDepth : this.maxRecursionDepth,
+                    seed: opts.seed !== undefined ? opts.seed : this.seed, sample0: opts.sample0 || 0,
+                    samplesPerRay: opts.samplesPerRay || 1, maxPaths: opts.maxPaths || 0 };
+        return colorAddon().color(this.handle, rays, opts.keys || null, p);
+    }
     destroy() {
         if (this.handle) addon().sceneDestroy(this.handle);
         this.handle = null;
@@ -138,4 +163,4 @@ class NodePixelBuffer {
 // Primitive carries the material and transform loadObjFile would be given).
 function attachObj(blob, objText, opts) { return addon().attachObj(blob, objText, opts || {}); }
 
-module.exports = { HipRenderer, NodePixelBuffer, addon, readHeader, attachObj, deviceForWorker, ABI_VERSION };
+module.exports = { HipRenderer, NodePixelBuffer, addon, colorAddon, readHeader, attachObj, deviceForWorker, ABI_VERSION };

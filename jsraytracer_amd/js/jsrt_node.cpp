@@ -12,6 +12,8 @@
 //   render(scene, params, rgba, progress?) -> Promise<stats>.  Runs in napi_create_async_work;
 //       progress arrives through a napi_threadsafe_function (N-API >= 4).
 //   deviceCount(), abiVersion()
+// (World.color of caller-supplied rays, include/jsrt_color.h, is a module of its own over the same scene handle:
+// jsrt_node_color.cpp)
 //
 // Errors: a negative jsrt_* return code becomes a thrown JS Error carrying jsrt_last_error()
 // (the reference throws strings, e.g. src/aggregates.js:39).  No C++ exception crosses N-API.
@@ -25,6 +27,7 @@
 #include "../../include/jsrt.h"
 #include "../../include/jsrt_json.h"
 #include "../../include/jsrt_mesh.h"
+#include "jsrt_node_scene.h"
 
 namespace {
 
@@ -114,21 +117,11 @@ napi_value stats_object(napi_env env, const jsrt_stats &st) {
     return o;
 }
 
-struct SceneBox {  // the external's payload: destroy is idempotent (explicit + GC finalizer)
-    jsrt_scene *s = nullptr;
-    int inflight = 0;              // async renders queued or running (all counted on the JS thread)
-    bool destroy_pending = false;  // sceneDestroy while renders were in flight: destroyed by the last
-};
+// (SceneBox, the external's payload, and get_scene: jsrt_node_scene.h, shared with jsrt_node_color.cpp)
 void box_finalize(napi_env, void *data, void *) {
     SceneBox *b = static_cast<SceneBox *>(data);
     if (b->s) jsrt_scene_destroy(b->s);
     delete b;
-}
-
-SceneBox *get_scene(napi_env env, napi_value v) {
-    void *p = nullptr;
-    if (napi_get_value_external(env, v, &p) != napi_ok || !p) return nullptr;
-    return static_cast<SceneBox *>(p);
 }
 
 napi_value SceneCreate(napi_env env, napi_callback_info info) {
@@ -282,10 +275,7 @@ void async_complete(napi_env env, napi_status, void *data) {
     }
     if (j->tsfn) napi_release_threadsafe_function(j->tsfn, napi_tsfn_release);
     if (j->buf_ref) napi_delete_reference(env, j->buf_ref);
-    if (j->box && --j->box->inflight == 0 && j->box->destroy_pending && j->box->s) {
-        jsrt_scene_destroy(j->box->s);  // sceneDestroy was called while this render ran
-        j->box->s = nullptr;
-    }
+    scene_job_done(j->box);  // (carries out a sceneDestroy called while this render ran)
     if (j->scene_ref) napi_delete_reference(env, j->scene_ref);
     napi_delete_async_work(env, j->work);
     delete j;

@@ -143,6 +143,64 @@ class Scene:
               "jsrt_material_color")
         return out
 
+    def color(self, rays, keys=None, *, max_depth=None, seed=1, sample0=0, spp=1, max_paths=0, stats=None):
+        """World.color (world.js:31-41) of caller-supplied rays (include/jsrt_color.h): rays n x 6 f32 (origin xyz
+        w=1, direction xyz w=0), keys n u32 (None: the ray's index); sample s of ray i draws from the keyed generator
+        at (seed, pixel = keys[i], sample = sample0 + s).  max_depth None: the blob's maxRecursionDepth; 0: black.
+        numpy in: (n, spp, 3) float32 out, through the host.  A torch tensor on the scene's device in: jsrt_color_device
+        on the current torch stream, a device tensor out, no host copy.  stats: a dict that receives the call's stats."""
+        L = _native.color_api()
+        spp = max(1, int(spp))
+        cp = _native.ColorParams(-1 if max_depth is None else int(max_depth), int(seed) & 0xFFFFFFFF, int(sample0), spp,
+                                 int(max_paths))
+        st = Stats() if stats is not None else None
+        st_ref = ctypes.byref(st) if st is not None else None
+        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):
+            rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+            n = len(rays)
+            if keys is not None:
+                keys = np.ascontiguousarray(keys, np.uint32).reshape(-1)
+                if len(keys) != n:
+                    raise JsrtError("keys must hold one key per ray")
+            out = np.empty((n, spp, 3), np.float32)
+            check(L.jsrt_color(self._h, rays.ctypes.data, keys.ctypes.data if keys is not None else None, n,
+                               ctypes.byref(cp), out.ctypes.data, st_ref), "jsrt_color")
+        else:
+            import torch
+            if not rays.is_cuda or rays.device.index != self.device:
+                raise JsrtError(f"rays must be on the scene's device (cuda:{self.device})")
+            rays = rays.to(torch.float32).contiguous().reshape(-1, 6)
+            n = rays.shape[0]
+            kt = None
+            if keys is not None:
+                if not hasattr(keys, "data_ptr"):
+                    keys = torch.as_tensor(np.ascontiguousarray(keys, np.uint32).view(np.int32), device=rays.device)
+                if keys.device != rays.device or keys.element_size() != 4 or keys.numel() != n:
+                    raise JsrtError("keys must be n 32-bit integers on the rays' device")
+                kt = keys.contiguous()
+            out = torch.empty((n, spp, 3), dtype=torch.float32, device=rays.device)
+            with torch.cuda.device(rays.device):
+                stream = torch.cuda.current_stream().cuda_stream
+                check(L.jsrt_color_device(self._h, rays.data_ptr() if n else None, kt.data_ptr() if kt is not None and n else None,
+                                          n, ctypes.byref(cp), out.data_ptr() if n else None, stream, st_ref),
+                      "jsrt_color_device")
+        if st is not None:
+            stats.update(st.as_dict())
+        return out
+
+    def camera_rays(self, width=0, height=0, kind=-1, seed=1, sample=0):
+        """The rays a render of width x height with renderer `kind` and `seed` starts for sample index `sample`
+        (include/jsrt_color.h jsrt_camera_rays; Camera.getRayForPixel with the sampling renderers' jitter and the
+        camera's depth-of-field draws): (H * W, 6) float32 in pixel order py * W + px."""
+        L = _native.color_api()
+        hdr = self.header()
+        W = width if width > 0 else hdr["width"]
+        H = height if height > 0 else hdr["height"]
+        p = self.params(W, H, kind=kind, seed=seed, device=self.device)
+        out = np.empty((H * W, 6), np.float32)
+        check(L.jsrt_camera_rays(self._h, ctypes.byref(p), int(sample), out.ctypes.data), "jsrt_camera_rays")
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             _native.lib().jsrt_scene_destroy(self._h)
