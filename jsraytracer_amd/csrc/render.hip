@@ -336,16 +336,6 @@ __global__ __launch_bounds__(256) void k_final(RenderArgs A, int32_t passes) {
 
 // ---------------------------------------------------------------------------------------------
 // host orchestration
-namespace {
-template <class T>
-T *carve(uint8_t *&p, size_t n) {
-    T *r = reinterpret_cast<T *>(p);
-    p += (n * sizeof(T) + 255) & ~(size_t)255;
-    return r;
-}
-size_t need(size_t n, size_t sz) { return (n * sz + 255) & ~(size_t)255; }
-}  // namespace
-
 void EventPairs::begin(hipStream_t s) {
     if (used == b.size()) {
         hipEvent_t x, y;
@@ -402,29 +392,10 @@ static FrameKnobs frame_knobs() {
     return K;
 }
 
-hipError_t Wavefront::reserve(size_t rays, size_t nodes, size_t hands, size_t paths, int mode, size_t shadow,
-                              const FrameKnobs &K) {
-    const bool tree = mode == SCHED_TREE, hybrid = mode == SCHED_HYBRID;
-    size_t bytes = 0;
-    bytes += 8 * need(rays, 4) + need(rays, 8) + 2 * need(rays, 4);  // o d addr key + t + prim ctx
-    if (tree) bytes += 2 * need(rays, 4);                            // path parent
-    if (hybrid) bytes += 3 * need(rays, 4) + need(rays, 1);          // parent, live lists, last levels
-    bytes += need(nodes, 16) + need(4 * nodes, 16);                  // node + child
-    if (tree) bytes += need(2 * nodes, 16);                          // slot
-    if (hybrid) bytes += need(nodes, 16);                            // slot (second children)
-    if (tree || hybrid) bytes += need(3 * paths, 4);                 // root
-    bytes += need(HAND_PLANES * hands, 16) + need(hands, 4) + need(64, 4);  // hand-off + nodes + level counts
-    bytes += need(64, 4) + need(2 * shadow, 16) + need(shadow, 16);  // work counters + shadow rays
-    // unstable spherePicks per level: ~1e-5 of the nodes (k_fix_dirs); every node under JSRT_FORCE_EXACT_PICK,
-    // or after a frame that ran out of records (fix_all: the frame is redone with one record per ray slot)
-    // (JSRT_FIX_CAP=n, a test knob: n records until a frame runs out, to exercise the redo on either pool)
-    const bool force_fix = K.force_exact_pick;
-    const size_t fixcap = fix_all ? rays + 4096 : K.fix_cap >= 0 ? (size_t)K.fix_cap : force_fix ? rays + 4096 : rays / 8 + 4096;
-    bytes += need(3 * fixcap, 16) + need(64, 4);
-    if (tree || hybrid)  // buckets
-        bytes += need(MAX_TREE_DEPTH * BKT_LEVEL, 4) + need((hands / 256 + 1) * BKT_N, 4) + need(rays, 4);
-    if (mem && bytes <= cap_bytes) {  // carve the cached allocation again
-    } else {
+hipError_t Wavefront::reserve(const PoolDims &d, const FrameKnobs &K) {
+    const size_t fixcap = fix_capacity(learned.fix_all, d.rays, K);
+    const size_t bytes = pool_bytes(d, fixcap);
+    if (!mem || bytes > cap_bytes) {  // (else: carve the cached allocation again)
         if (mem) (void)hipFree(mem);
         mem = nullptr;
         cap_bytes = 0;
@@ -432,42 +403,8 @@ hipError_t Wavefront::reserve(size_t rays, size_t nodes, size_t hands, size_t pa
         if (e != hipSuccess) return e;
         cap_bytes = bytes;
     }
-    uint8_t *p = static_cast<uint8_t *>(mem);
-    WArgs &w = args;
-    w = WArgs{};
-    w.ox = carve<float>(p, rays); w.oy = carve<float>(p, rays); w.oz = carve<float>(p, rays);
-    w.dx = carve<float>(p, rays); w.dy = carve<float>(p, rays); w.dz = carve<float>(p, rays);
-    w.addr = carve<uint32_t>(p, rays); w.key = carve<uint32_t>(p, rays);
-    w.t = carve<double>(p, rays); w.prim = carve<int32_t>(p, rays); w.ctx = carve<int32_t>(p, rays);
-    if (tree) { w.path = carve<uint32_t>(p, rays); w.parent = carve<uint32_t>(p, rays); }
-    if (hybrid) {
-        w.parent = carve<uint32_t>(p, rays);
-        w.list0 = carve<uint32_t>(p, rays);
-        w.list1 = carve<uint32_t>(p, rays);
-        w.endl = carve<uint8_t>(p, rays);
-    }
-    w.node = carve<float4>(p, nodes);
-    w.child = carve<float4>(p, 4 * nodes);
-    if (tree) w.slot = carve<float4>(p, 2 * nodes);
-    if (hybrid) w.slot = carve<float4>(p, nodes);
-    if (tree || hybrid) w.root = carve<float>(p, 3 * paths);
-    w.hand = carve<float4>(p, HAND_PLANES * hands);
-    w.hnode = carve<uint32_t>(p, hands);
-    w.lvl = carve<uint32_t>(p, 64);
-    w.qctr = carve<uint32_t>(p, 64);
-    w.fixrec = carve<uint4>(p, 3 * fixcap);
-    w.fixctr = carve<uint32_t>(p, 64);
-    w.fixcap = (uint32_t)fixcap;
-    w.force_fix = force_fix ? 1 : 0;
-    if (shadow) { w.sray = carve<float4>(p, 2 * shadow); w.scol = carve<float4>(p, shadow); }
-    if (tree || hybrid) {
-        w.bkt = carve<uint32_t>(p, MAX_TREE_DEPTH * BKT_LEVEL);
-        w.bbase = carve<uint32_t>(p, (hands / 256 + 1) * BKT_N);
-        w.brank = carve<uint32_t>(p, rays);
-    }
-    w.nstride = nodes;
-    w.hstride = hands;
-    w.sstride = shadow;
+    carve_pool(args, d, fixcap, static_cast<uint8_t *>(mem));
+    args.force_fix = K.force_exact_pick ? 1 : 0;
     return hipSuccess;
 }
 
@@ -487,35 +424,9 @@ Wavefront::~Wavefront() {
     if (ev_shadow) (void)hipEventDestroy(ev_shadow);
 }
 
-// The schedule of a scene's frames: chain when no node can have two children; otherwise the hybrid chain
-// (side chains for second children) for flat scenes, the tree for BVH / SDF scenes (JSRT_HYBRID=0/1 forces
-// one).  A/B on MI355X (profiles/r04_s6_ab.txt): cornell hybrid 493.8 vs tree 466.3 Ms/s; bunny 518.4 vs
-// 555.7, dragon 785.4 vs 792.5, SDF_Menger 112.8 vs 116.1 -- the tree's octant-sorted appends keep BVH
-// casts coherent, and its compaction suits sky-heavy scenes.
-static int schedule_of(const DScene &S, const FrameKnobs &K) {
-    if (S.max_children <= 1) return SCHED_CHAIN;
-    if (K.hybrid >= 0) return K.hybrid ? SCHED_HYBRID : SCHED_TREE;
-    return S.profile == PF_ANALYTIC ? SCHED_HYBRID : SCHED_TREE;
-}
-constexpr size_t HYBRID_POOL_FACTOR = 2;  // initial hybrid side-chain slots: paths x factor / 4
-
 size_t wavefront_bytes_per_path(const DScene &S, int ns, int max_depth) {
-    const size_t ray = 8 * 4 + 8 + 2 * 4, node = 16 + 4 * 16, hand = HAND_PLANES * 16 + 4;
-    const bool persist = (S.profile & PF_SDF) && S.all_roots_prims;
-    size_t group = 1;
-    while ((int)group < ns && ns <= 64) group *= 2;
-    const int sched = schedule_of(S, frame_knobs());
-    const size_t depth = (size_t)std::max(1, max_depth);
-    if (sched == SCHED_CHAIN)  // chain: one ray and depth nodes per path
-        return ray + depth * node + hand + (persist ? group * 48 : 0);
-    if (sched == SCHED_HYBRID)  // per chain slot: ray + parent + rank, depth x (node + second-child slot), hand-off
-        return (4 + HYBRID_POOL_FACTOR) * (ray + 17 + depth * (node + 16) + hand + (persist ? group * 48 : 0) +
-                                           BKT_N * 4 / 256) / 4 + 12;
-    const size_t pool = 8, level_cap = pool / 2;  // render_frame: pool = 8 x paths, level_cap = pool / 2
-    // + the bucketed hand-off's ranks (4 B per pool slot) and block bases (BKT_N words per 256 hand-off slots)
-    return pool * (ray + 8 + node + 2 * 16 + 4) + level_cap * (hand + (persist ? group * 48 : 0) + BKT_N * 4 / 256) + 12;
+    return pool_bytes_per_path(S, ns, max_depth, schedule_of(S, frame_knobs()));
 }
-
 
 // Grid of a persistent kernel: as many 256-thread blocks as the device keeps resident (occupancy x
 // CUs), never more than the work needs.  Cached per kernel and device behind a mutex: renders run
@@ -543,69 +454,47 @@ unsigned persistent_grid(const void *kernel, size_t work) {
 }
 
 // instantiated in render_pf.hip, one translation unit per profile
-extern template void run_batch<PF_ANALYTIC, true>(const DScene &, const RenderArgs &, const WArgs &, hipStream_t,
-                                         KernelTimes *, const std::vector<size_t> &, const BatchSync *);
-extern template void run_batch<PF_ANALYTIC, false>(const DScene &, const RenderArgs &, const WArgs &, hipStream_t,
-                                         KernelTimes *, const std::vector<size_t> &, const BatchSync *);
-extern template void run_batch<PF_MESH, true>(const DScene &, const RenderArgs &, const WArgs &, hipStream_t,
-                                         KernelTimes *, const std::vector<size_t> &, const BatchSync *);
-extern template void run_batch<PF_MESH, false>(const DScene &, const RenderArgs &, const WArgs &, hipStream_t,
-                                         KernelTimes *, const std::vector<size_t> &, const BatchSync *);
-extern template void run_batch<PF_SDF, true>(const DScene &, const RenderArgs &, const WArgs &, hipStream_t,
-                                         KernelTimes *, const std::vector<size_t> &, const BatchSync *);
-extern template void run_batch<PF_SDF, false>(const DScene &, const RenderArgs &, const WArgs &, hipStream_t,
-                                         KernelTimes *, const std::vector<size_t> &, const BatchSync *);
-extern template void run_batch<PF_ALL, true>(const DScene &, const RenderArgs &, const WArgs &, hipStream_t,
-                                         KernelTimes *, const std::vector<size_t> &, const BatchSync *);
-extern template void run_batch<PF_ALL, false>(const DScene &, const RenderArgs &, const WArgs &, hipStream_t,
-                                         KernelTimes *, const std::vector<size_t> &, const BatchSync *);
+#define JSRT_PF_EXTERN(PFV)                                                                                            \
+    extern template void run_batch<PFV, true>(const DScene &, const RenderArgs &, const WArgs &, hipStream_t,          \
+                                              KernelTimes *, const std::vector<size_t> &, const BatchSync *);          \
+    extern template void run_batch<PFV, false>(const DScene &, const RenderArgs &, const WArgs &, hipStream_t,         \
+                                               KernelTimes *, const std::vector<size_t> &, const BatchSync *);         \
+    extern template void cast_rays_pf<PFV>(const DScene &, const float *, uint32_t, double, double, int, double *,     \
+                                           int32_t *, hipStream_t);                                                    \
+    extern template bool cast_path_pf<PFV>(const DScene &, int, const float *, uint32_t, double, double, int,          \
+                                           uint32_t *, double *, int32_t *, hipStream_t);                              \
+    extern template void material_data_pf<PFV>(const DScene &, const float *, uint32_t, double *, int32_t *, float *,  \
+                                               float *, float *, float *, float *, hipStream_t);                       \
+    extern template void material_uv_pf<PFV>(const DScene &, const float *, uint32_t, float *, int32_t *, hipStream_t);
+JSRT_PF_EXTERN(PF_ANALYTIC)
+JSRT_PF_EXTERN(PF_MESH)
+JSRT_PF_EXTERN(PF_SDF)
+JSRT_PF_EXTERN(PF_ALL)
+#undef JSRT_PF_EXTERN
 
-#define JSRT_CAST_EXTERN(PFV) \
-    extern template void cast_rays_pf<PFV>(const DScene &, const float *, uint32_t, double, double, int, double *, \
-                                           int32_t *, hipStream_t);
-JSRT_CAST_EXTERN(PF_ANALYTIC)
-JSRT_CAST_EXTERN(PF_MESH)
-JSRT_CAST_EXTERN(PF_SDF)
-JSRT_CAST_EXTERN(PF_ALL)
-#undef JSRT_CAST_EXTERN
-
-#define JSRT_MD_EXTERN(PFV)                                                                                          \
-    extern template void material_data_pf<PFV>(const DScene &, const float *, uint32_t, double *, int32_t *, float *, \
-                                               float *, float *, float *, float *, hipStream_t);
-JSRT_MD_EXTERN(PF_ANALYTIC)
-JSRT_MD_EXTERN(PF_MESH)
-JSRT_MD_EXTERN(PF_SDF)
-JSRT_MD_EXTERN(PF_ALL)
-#undef JSRT_MD_EXTERN
+// f(std::integral_constant<int, PF>) for the scene's kernel profile: the one switch over the instantiations above
+template <class F>
+static void with_profile(int profile, F &&f) {
+    switch (profile) {
+    case PF_ANALYTIC: f(std::integral_constant<int, PF_ANALYTIC>{}); break;
+    case PF_MESH: f(std::integral_constant<int, PF_MESH>{}); break;
+    case PF_SDF: f(std::integral_constant<int, PF_SDF>{}); break;
+    default: f(std::integral_constant<int, PF_ALL>{}); break;
+    }
+}
 
 hipError_t material_data_rays(const DScene &S, const float *d_rays, uint32_t n, double *d_t, int32_t *d_prim,
                               float *d_nrm, float *d_pos, float *d_uv, float *d_bary, float *d_bc, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    switch (S.profile) {
-    case PF_ANALYTIC: material_data_pf<PF_ANALYTIC>(S, d_rays, n, d_t, d_prim, d_nrm, d_pos, d_uv, d_bary, d_bc, st); break;
-    case PF_MESH: material_data_pf<PF_MESH>(S, d_rays, n, d_t, d_prim, d_nrm, d_pos, d_uv, d_bary, d_bc, st); break;
-    case PF_SDF: material_data_pf<PF_SDF>(S, d_rays, n, d_t, d_prim, d_nrm, d_pos, d_uv, d_bary, d_bc, st); break;
-    default: material_data_pf<PF_ALL>(S, d_rays, n, d_t, d_prim, d_nrm, d_pos, d_uv, d_bary, d_bc, st); break;
-    }
+    with_profile(S.profile, [&](auto pf) {
+        material_data_pf<decltype(pf)::value>(S, d_rays, n, d_t, d_prim, d_nrm, d_pos, d_uv, d_bary, d_bc, st);
+    });
     return hipGetLastError();
 }
 
-#define JSRT_MUV_EXTERN(PFV) \
-    extern template void material_uv_pf<PFV>(const DScene &, const float *, uint32_t, float *, int32_t *, hipStream_t);
-JSRT_MUV_EXTERN(PF_ANALYTIC)
-JSRT_MUV_EXTERN(PF_MESH)
-JSRT_MUV_EXTERN(PF_SDF)
-JSRT_MUV_EXTERN(PF_ALL)
-#undef JSRT_MUV_EXTERN
-
 hipError_t material_uv_rays(const DScene &S, const float *d_rays, uint32_t n, float *d_uv, int32_t *d_has, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    switch (S.profile) {
-    case PF_ANALYTIC: material_uv_pf<PF_ANALYTIC>(S, d_rays, n, d_uv, d_has, st); break;
-    case PF_MESH: material_uv_pf<PF_MESH>(S, d_rays, n, d_uv, d_has, st); break;
-    case PF_SDF: material_uv_pf<PF_SDF>(S, d_rays, n, d_uv, d_has, st); break;
-    default: material_uv_pf<PF_ALL>(S, d_rays, n, d_uv, d_has, st); break;
-    }
+    with_profile(S.profile, [&](auto pf) { material_uv_pf<decltype(pf)::value>(S, d_rays, n, d_uv, d_has, st); });
     return hipGetLastError();
 }
 
@@ -646,56 +535,262 @@ hipError_t cast_rays(const DScene &S, const float *d_rays, uint32_t n, double mi
                      double *d_t, int32_t *d_prim, hipStream_t st) {
     if (n == 0) return hipSuccess;
     const int tr = transparent ? 1 : 0;
-    switch (S.profile) {
-    case PF_ANALYTIC: cast_rays_pf<PF_ANALYTIC>(S, d_rays, n, min_dist, max_dist, tr, d_t, d_prim, st); break;
-    case PF_MESH: cast_rays_pf<PF_MESH>(S, d_rays, n, min_dist, max_dist, tr, d_t, d_prim, st); break;
-    case PF_SDF: cast_rays_pf<PF_SDF>(S, d_rays, n, min_dist, max_dist, tr, d_t, d_prim, st); break;
-    default: cast_rays_pf<PF_ALL>(S, d_rays, n, min_dist, max_dist, tr, d_t, d_prim, st); break;
-    }
+    with_profile(S.profile, [&](auto pf) { cast_rays_pf<decltype(pf)::value>(S, d_rays, n, min_dist, max_dist, tr, d_t, d_prim, st); });
     return hipGetLastError();
 }
-
-#define JSRT_CASTPATH_EXTERN(PFV) \
-    extern template bool cast_path_pf<PFV>(const DScene &, int, const float *, uint32_t, double, double, int, uint32_t *, \
-                                           double *, int32_t *, hipStream_t);
-JSRT_CASTPATH_EXTERN(PF_ANALYTIC)
-JSRT_CASTPATH_EXTERN(PF_MESH)
-JSRT_CASTPATH_EXTERN(PF_SDF)
-JSRT_CASTPATH_EXTERN(PF_ALL)
-#undef JSRT_CASTPATH_EXTERN
 
 hipError_t cast_rays_path(const DScene &S, int path, const float *d_rays, uint32_t n, double min_dist, double max_dist,
                           bool transparent, uint32_t *d_ctr, double *d_t, int32_t *d_prim, hipStream_t st, bool *have) {
     *have = true;
     if (n == 0) return hipSuccess;
     const int tr = transparent ? 1 : 0;
-    // the persistent march serves SDF scenes whose roots are all Primitives (render_frame's `persist`), the
+    // the persistent march serves SDF scenes whose roots are all Primitives (plan_batches' `persist`), the
     // node-per-lane shadow cast flat scenes (every root a Primitive, no SDF: cast_path_pf)
     if ((path == CAST_PATH_PERSISTENT || path == CAST_PATH_PERSISTENT_ANY || path == CAST_PATH_ANY_NODE) && !S.all_roots_prims) {
         *have = false;
         return hipSuccess;
     }
-    switch (S.profile) {
-    case PF_ANALYTIC: *have = cast_path_pf<PF_ANALYTIC>(S, path, d_rays, n, min_dist, max_dist, tr, d_ctr, d_t, d_prim, st); break;
-    case PF_MESH: *have = cast_path_pf<PF_MESH>(S, path, d_rays, n, min_dist, max_dist, tr, d_ctr, d_t, d_prim, st); break;
-    case PF_SDF: *have = cast_path_pf<PF_SDF>(S, path, d_rays, n, min_dist, max_dist, tr, d_ctr, d_t, d_prim, st); break;
-    default: *have = cast_path_pf<PF_ALL>(S, path, d_rays, n, min_dist, max_dist, tr, d_ctr, d_t, d_prim, st); break;
-    }
+    with_profile(S.profile, [&](auto pf) {
+        *have = cast_path_pf<decltype(pf)::value>(S, path, d_rays, n, min_dist, max_dist, tr, d_ctr, d_t, d_prim, st);
+    });
     return hipGetLastError();
 }
 
 namespace {
-template <bool CHAIN>
-void run_batch_pf(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t st, KernelTimes *kt,
-                  const std::vector<size_t> &bound, const BatchSync *sync) {
-    switch (S.profile) {
-    case PF_ANALYTIC: run_batch<PF_ANALYTIC, CHAIN>(S, A, W, st, kt, bound, sync); break;
-    case PF_MESH: run_batch<PF_MESH, CHAIN>(S, A, W, st, kt, bound, sync); break;
-    case PF_SDF: run_batch<PF_SDF, CHAIN>(S, A, W, st, kt, bound, sync); break;
-    default: run_batch<PF_ALL, CHAIN>(S, A, W, st, kt, bound, sync); break;
+// What a frame holds on the host beside its pools: the pinned read-back of the level counts (tree / hybrid
+// schedule) and the frame flags of both pools, and the four events that order the two batch streams.  Freed on
+// every exit of trace_frame.
+struct FrameHost {
+    uint32_t *h_lvl = nullptr;
+    hipEvent_t ev_start = nullptr, ev_end = nullptr, ev_acc[2] = {nullptr, nullptr};
+    ~FrameHost() {
+        if (h_lvl) (void)hipHostFree(h_lvl);
+        for (hipEvent_t x : {ev_start, ev_end, ev_acc[0], ev_acc[1]})
+            if (x) (void)hipEventDestroy(x);
     }
-}
+};
 }  // namespace
+
+// The batches of a frame of npix_total pixels (run_frame below), attempt after attempt until none is poisoned.  The
+// arithmetic -- plan, schedule, pool shape, launch bounds, settings, what a redo changes -- is render_plan.h's; here
+// are the streams, the events, the twin pool, the memsets, the batch loop and the read-back of the flags.
+// aborted: the callback ended the frame, which is then left as the last preview had it.
+static hipError_t trace_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront &wf, hipStream_t st, KernelTimes *kt,
+                              size_t max_paths, const std::function<bool(int, double, bool)> &progress,
+                              const std::function<bool()> &due, const RayFeed *feed, uint32_t npix_total, bool &aborted) {
+    const FrameKnobs K = frame_knobs();  // per frame: a process may change its environment between renders
+    const BatchPlan plan = plan_batches(S, A, ns, max_paths, K);
+    RenderArgs At = A;
+    At.tile_p = plan.tile_p;
+    // Chain schedule when no node can have two children: depth x paths node records, nothing can
+    // overflow, batches are enqueued back to back.  Tree schedule otherwise: a ray pool for all
+    // levels of a batch (one level may hold half of it), compacted level by level.  Its launches
+    // are sized by level counts learned from the scene's first batch (one read-back per scene and
+    // batch shape) with a margin; a batch that outgrows its pool (LVL_FLAG) or a launch bound
+    // (LVL_UNDER) poisons the frame, which is redone with a larger pool / conservative bounds.
+    // The frame flags are read once, after the last batch.
+    // Hybrid chain (branching materials, the default): the chain layout -- ray slot = path, node [L * cap +
+    // slot], no parent / path planes, one bottom-up resolve -- plus a side chain per second child (a slot
+    // appended after the paths, cap = paths + paths x pool_factor / 4).  Its level counts (the side chains
+    // started so far) live on the device; launch bounds, overflow and redo work as for the tree.
+    const int sched = schedule_of(S, K);
+    const bool hybrid = sched == SCHED_HYBRID, chain = sched != SCHED_TREE, learned = sched != SCHED_CHAIN;
+    const int depth = std::max(1, A.max_depth);
+    const size_t paths = (size_t)plan.npix * plan.nsb;
+    LearnedPool &lp = wf.learned;
+    if (learned && (lp.pool_paths != paths || lp.pool_mode != sched)) {  // learned pool / bounds: per batch shape
+        lp.pool_factor = initial_pool_factor(sched, paths, K);
+        lp.frac.clear();
+        lp.pool_paths = paths;
+        lp.pool_mode = sched;
+    }
+    hipError_t e = hipSuccess;
+    FrameHost H;
+    if ((e = hipHostMalloc((void **)&H.h_lvl, 128 * sizeof(uint32_t), 0)) != hipSuccess) return e;
+    // Two batch pools on two streams: consecutive batches alternate between them, so one batch's levels
+    // (latency-bound casts, VALU-bound shadow samples, their launch tails) overlap the other's.  Only the
+    // accumulation into A.accum is ordered across them -- each batch's k_accum / k_resolve waits for the
+    // previous batch's (renderers.js:93-97: samples in order) -- so the image is unchanged bit for bit.
+    // (A/B on MI355X, profiles/r03_s18_ab.txt: cornell +12.5 %, the dragon +2.6 %, bunny +0.6 %; two
+    // persistent SDF marches side by side lose 1 %, so SDF scenes with persistent casts run on one
+    // stream.)  The twin pool is allocated only if it fits; otherwise the frame runs on one pool.
+    const uint32_t rows = batch_rows(plan, (uint32_t)A.spp), cols = batch_cols(plan, npix_total);  // render_plan.h
+    const uint64_t nbatches = (uint64_t)rows * cols;
+    // A render that asks for its launches' own times (JSRT_EVENTS_ONE_STREAM) runs on one stream: a
+    // launch's event interval is only its own time when no other batch's kernels share the CUs.
+    const bool timed_launches = kt && kt->one_stream;
+    // two streams need two batches of comparable size (render_plan.h two_full)
+    bool dual = !timed_launches && nbatches > 1 &&
+                (K.dual >= 0 ? K.dual == 1 : (!plan.persist && two_full(plan, npix_total, (uint32_t)A.spp)));
+    if (dual) {
+        if (!wf.twin) wf.twin = new Wavefront();
+        if (!wf.side) e = hipStreamCreateWithFlags(&wf.side, hipStreamNonBlocking);
+        for (hipEvent_t *x : {&H.ev_start, &H.ev_end, &H.ev_acc[0], &H.ev_acc[1]})
+            if (e == hipSuccess) e = hipEventCreateWithFlags(x, hipEventDisableTiming);
+        if (e != hipSuccess) return e;
+    }
+    hipStream_t st2 = dual ? wf.side : st;
+    // A frame with persistent SDF casts (one stream) runs k_shadow on a stream of its own (BatchSync::aux):
+    // level L's shadow samples overlap level L + 1's march.  SDF_Menger +6.5 %; elsewhere it loses
+    // (bunny on one stream -5 %; beside two batch streams cornell +-0, dragon -1.3 %; profiles/
+    // r03_s18_ab.txt s22, s26).  JSRT_SPLIT=0/1 forces it.
+    const bool split = !timed_launches && ns > 0 && (K.split >= 0 ? K.split == 1 : (plan.persist && !dual));
+    auto aux_of = [&](Wavefront &w) -> hipError_t {
+        hipError_t r = hipSuccess;
+        if (!w.aux) r = hipStreamCreateWithFlags(&w.aux, hipStreamNonBlocking);
+        if (r == hipSuccess && !w.ev_shade) r = hipEventCreateWithFlags(&w.ev_shade, hipEventDisableTiming);
+        if (r == hipSuccess && !w.ev_shadow) r = hipEventCreateWithFlags(&w.ev_shadow, hipEventDisableTiming);
+        return r;
+    };
+    if (split && (e = aux_of(wf)) == hipSuccess && dual) e = aux_of(*wf.twin);
+    if (e != hipSuccess) return e;
+    bool conservative = false;
+    double reported = 0;  // completion already reported: a redone frame reports only beyond it
+    for (int attempt = 0; e == hipSuccess; ++attempt) {
+        if (kt) kt->attempts = (uint32_t)attempt + 1;
+        const PoolShape shape = pool_shape(sched, paths, depth, lp.pool_factor, ns, plan.persist, K);
+        if (!shape.fits) { e = hipErrorOutOfMemory; break; }  // u32 node index
+        e = wf.reserve(shape.dims, K);
+        if (e == hipSuccess && dual) {
+            const hipError_t e2 = wf.twin->reserve(shape.dims, K);
+            if (e2 == hipErrorOutOfMemory) {  // no room for a second pool: one pool, one stream
+                (void)hipGetLastError();
+                wf.twin->release();
+                dual = false;
+                st2 = st;
+            } else {
+                e = e2;
+            }
+        }
+        if (e != hipSuccess) break;
+        WArgs W = wf.args;
+        batch_settings(W, S, K, plan, shape, ns, sched);
+        WArgs W2 = W;  // the twin pool: the same settings over its own buffers
+        if (dual) {
+            W2 = wf.twin->args;
+            batch_settings(W2, S, K, plan, shape, ns, sched);
+        }
+        if (!feed && (e = hipMemsetAsync(A.accum, 0, (size_t)A.ncols * A.H * 4 * sizeof(float), st)) != hipSuccess) break;
+        if ((e = hipMemsetAsync(W.lvl + LVL_UNDER, 0, 2 * sizeof(uint32_t), st)) != hipSuccess) break;  // frame flags
+        if ((e = hipMemsetAsync(W.fixctr, 0, sizeof(uint32_t), st)) != hipSuccess) break;
+        if (dual && (e = hipMemsetAsync(W2.fixctr, 0, sizeof(uint32_t), st)) != hipSuccess) break;
+        if (dual) {  // the side stream starts after everything enqueued on st so far
+            if ((e = hipEventRecord(H.ev_start, st)) != hipSuccess || (e = hipStreamWaitEvent(st2, H.ev_start, 0)) != hipSuccess) break;
+            if ((e = hipMemsetAsync(W2.lvl + LVL_UNDER, 0, 2 * sizeof(uint32_t), st2)) != hipSuccess) break;
+        }
+        // the frame flags (and, for progress, level counts) of both pools, read back after both streams idle
+        auto read_flags = [&]() -> hipError_t {
+            hipError_t r;
+            if (dual && ((r = hipEventRecord(H.ev_end, st2)) != hipSuccess || (r = hipStreamWaitEvent(st, H.ev_end, 0)) != hipSuccess))
+                return r;
+            if ((r = hipMemcpyAsync(H.h_lvl, W.lvl, 64 * sizeof(uint32_t), hipMemcpyDeviceToHost, st)) != hipSuccess) return r;
+            if (dual && (r = hipMemcpyAsync(H.h_lvl + 64, W2.lvl, 64 * sizeof(uint32_t), hipMemcpyDeviceToHost, st)) != hipSuccess)
+                return r;
+            return hipStreamSynchronize(st);
+        };
+        auto flagged = [&](int k) { return H.h_lvl[k] != 0 || (dual && H.h_lvl[64 + k] != 0); };
+        uint64_t bi = 0;  // batch index: even batches on (W, st), odd ones on (W2, st2)
+        const uint64_t total = (uint64_t)npix_total * A.spp;
+        uint64_t done = 0;
+        // stop: the callback aborted the frame.  redo_now: a progress check found a batch poisoned -- the frame is
+        // redone at once instead of after its last batch, so that every pass is reported exactly once and from a
+        // clean frame (a multi-rank caller keeps its collectives in step on the passes, tiles.render_progressive)
+        bool stop = false, redo_now = false;
+        // A due callback: wait for the batches so far and report `pass` from a clean frame.  false ends the batch
+        // loop (an error in e, a poisoned batch, or the callback's abort).
+        auto report = [&](int pass) {
+            if ((e = read_flags()) != hipSuccess) return false;
+            if (flagged(LVL_FLAG) || flagged(LVL_UNDER)) {
+                redo_now = true;
+                return false;
+            }
+            const double c = (double)done / (double)total;
+            if (c > reported) {
+                reported = c;
+                stop = !progress(pass, c, true);
+            }
+            return !stop;
+        };
+        for (uint32_t row = 0; row < rows && e == hipSuccess && !stop && !redo_now; ++row) {
+            const BatchSpan r0 = batch_span(plan, npix_total, (uint32_t)A.spp, row, 0);
+            const uint32_t s0 = r0.s0, nb = r0.nb;  // the row's samples
+            for (uint32_t col = 0; col < cols; ++col, ++bi) {
+                const BatchSpan span = batch_span(plan, npix_total, (uint32_t)A.spp, row, col);
+                const bool odd = dual && (bi & 1);
+                WArgs &Wb = odd ? W2 : W;
+                const hipStream_t sb = odd ? st2 : st;
+                Wb.p0 = span.p0;
+                Wb.npix = span.npix;
+                Wb.s0 = span.s0;
+                Wb.npaths = span.npix * span.nb;
+                Wb.cap = hybrid ? (uint32_t)shape.cap : Wb.npaths;
+                const std::vector<size_t> bound =
+                    learned ? level_bounds(sched, Wb.npaths, shape, A.max_depth, S.max_children, lp.frac, conservative, K)
+                            : std::vector<size_t>();
+                BatchSync sync;
+                sync.feed = feed;
+                if (dual) {
+                    sync.wait = bi > 0 ? H.ev_acc[(bi - 1) & 1] : nullptr;
+                    sync.done = H.ev_acc[bi & 1];
+                }
+                if (split) {
+                    Wavefront &pw = odd ? *wf.twin : wf;
+                    sync.aux = pw.aux;
+                    sync.shade_done = pw.ev_shade;
+                    sync.shadow_done = pw.ev_shadow;
+                }
+                with_profile(S.profile, [&](auto pf) {
+                    if (chain) run_batch<decltype(pf)::value, true>(S, At, Wb, sb, kt, bound, &sync);
+                    else run_batch<decltype(pf)::value, false>(S, At, Wb, sb, kt, bound, &sync);
+                });
+                if ((e = hipGetLastError()) != hipSuccess) break;
+                done += (uint64_t)Wb.npix * nb;
+                if (kt) ++kt->batches;
+                // Simple / RandomMultisampling report {pass: 0, completion: pixels done / total} from inside
+                // their pixel loop (renderers.js:28-37): here after a batch, when a callback is due (the
+                // host's timelimit clock is checked first: no sync otherwise)
+                if (progress && A.kind != JSRT_RENDERER_INCREMENTAL && (!due || due()) && !report(0)) break;
+                if (learned && (lp.frac.empty() || conservative)) {
+                    // learn the level counts: from the scene's first batch, or -- when that batch was
+                    // not representative and a frame had to be redone -- as the maximum over every
+                    // batch of the conservative redo, so later frames of this shape are not redone
+                    if ((e = hipMemcpyAsync(H.h_lvl, Wb.lvl, 64 * sizeof(uint32_t), hipMemcpyDeviceToHost, sb)) != hipSuccess) break;
+                    if ((e = hipStreamSynchronize(sb)) != hipSuccess) break;
+                    learn_fractions(lp.frac, H.h_lvl, A.max_depth, hybrid, Wb.npaths);
+                }
+            }
+            // Incremental: wait for the pass
+            if (e == hipSuccess && progress && A.kind == JSRT_RENDERER_INCREMENTAL && (!due || due()) && !report((int)(s0 + nb - 1)))
+                break;
+        }
+        if (e != hipSuccess) break;
+        if (stop) {  // an aborted frame is not redone (read_flags joins the side stream into st and waits for it)
+            e = read_flags();
+            aborted = true;
+            break;
+        }
+        // The frame flags of both pools, every schedule.  read_flags also joins the side stream into st, so the
+        // caller's stream orders after every batch of the frame (k_final, and the caller's own work after
+        // jsrt_render_device returns).  A frame that ended with a batch poisoned is redone, never returned: in
+        // the round-4 draft of the hybrid chain this loop broke out for every chain-layout schedule before
+        // reading the flags, so a hybrid frame whose side chains outgrew their slots came back with its
+        // poisoned batches' pixels missing (DESIGN.md §4.1, tests/test_gpu_redo_streams.py).
+        if ((e = read_flags()) != hipSuccess) break;
+        const bool flag = flagged(LVL_FLAG), under = flagged(LVL_UNDER);
+        if (!flag && !under) break;
+        if (redo_step(lp, wf.twin ? &wf.twin->learned.fix_all : nullptr, sched, paths, flag, under, conservative) ==
+            Redo::OUT_OF_MEMORY) {
+            e = hipErrorOutOfMemory;
+            break;
+        }
+        if (kt) kt->reset();
+    }
+    if (e != hipSuccess && dual) {  // nothing of this frame may still run on the side stream
+        (void)hipStreamSynchronize(st2);
+        (void)hipStreamSynchronize(st);
+    }
+    return e;
+}
 
 // A frame's batches: the camera's paths of the owned pixels into A.accum (render_frame), or -- feed -- World.color of
 // the caller's rays into feed->out (color_frame), where a "pixel" of the plan is a ray and nothing of the pixel order
@@ -715,311 +810,8 @@ static hipError_t run_frame(const DScene &S, const RenderArgs &A, int ns, Wavefr
         }
         return hipSuccess;
     }
-    const FrameKnobs K = frame_knobs();  // per frame: a process may change its environment between renders
-    const BatchPlan plan = plan_batches(S, A, ns, max_paths, K);
-    const uint32_t npix = plan.npix, nsb = plan.nsb;
-    const bool persist = plan.persist;
-    RenderArgs At = A;
-    At.tile_p = plan.tile_p;
-    // Chain schedule when no node can have two children: depth x paths node records, nothing can
-    // overflow, batches are enqueued back to back.  Tree schedule otherwise: a ray pool for all
-    // levels of a batch (one level may hold half of it), compacted level by level.  Its launches
-    // are sized by level counts learned from the scene's first batch (one read-back per scene and
-    // batch shape) with a margin; a batch that outgrows its pool (LVL_FLAG) or a launch bound
-    // (LVL_UNDER) poisons the frame, which is redone with a larger pool / conservative bounds.
-    // The frame flags are read once, after the last batch.
-    // Hybrid chain (branching materials, the default): the chain layout -- ray slot = path, node [L * cap +
-    // slot], no parent / path planes, one bottom-up resolve -- plus a side chain per second child (a slot
-    // appended after the paths, cap = paths + paths x pool_factor / 4).  Its level counts (the side chains
-    // started so far) live on the device; launch bounds, overflow and redo work as for the tree.
-    const int sched = schedule_of(S, K);
-    const bool hybrid = sched == SCHED_HYBRID, chain = sched != SCHED_TREE, learned = sched != SCHED_CHAIN;
-    const int depth = std::max(1, A.max_depth);
-    const size_t paths = (size_t)npix * nsb;
-    // test knobs: a smaller first pool / tighter learned bounds exercise the frame redo paths
-    const double margin = K.bound_margin;
-    const size_t slack = K.bound_slack;
-    if (learned && (wf.pool_paths != paths || wf.pool_mode != sched)) {  // learned pool / bounds: per batch shape
-        // (a batch of at most 1 M paths starts with 3 side-chain slots per path: a band of columns through a
-        // glass sphere outgrows the default 0.5 -- a redo the memory of small batches need not risk)
-        wf.pool_factor = K.pool_factor ? K.pool_factor : (hybrid ? (paths <= ((size_t)1 << 20) ? 8 : HYBRID_POOL_FACTOR) : 8);
-        wf.frac.clear();
-        wf.pool_paths = paths;
-        wf.pool_mode = sched;
-    }
-    hipError_t e = hipSuccess;
-    uint32_t *h_lvl = nullptr;  // read-back of the level counts (tree / hybrid schedule) and the frame flags
-    if ((e = hipHostMalloc((void **)&h_lvl, 128 * sizeof(uint32_t), 0)) != hipSuccess) return e;
-    // Two batch pools on two streams: consecutive batches alternate between them, so one batch's levels
-    // (latency-bound casts, VALU-bound shadow samples, their launch tails) overlap the other's.  Only the
-    // accumulation into A.accum is ordered across them -- each batch's k_accum / k_resolve waits for the
-    // previous batch's (renderers.js:93-97: samples in order) -- so the image is unchanged bit for bit.
-    // (A/B on MI355X, profiles/r03_s18_ab.txt: cornell +12.5 %, the dragon +2.6 %, bunny +0.6 %; two
-    // persistent SDF marches side by side lose 1 %, so SDF scenes with persistent casts run on one
-    // stream.)  The twin pool is allocated only if it fits; otherwise the frame runs on one pool.
-    const uint32_t rows = batch_rows(plan, (uint32_t)A.spp), cols = batch_cols(plan, npix_total);  // render_plan.h
-    const uint64_t nbatches = (uint64_t)rows * cols;
-    // A render that asks for its launches' own times (JSRT_EVENTS_ONE_STREAM) runs on one stream: a
-    // launch's event interval is only its own time when no other batch's kernels share the CUs.
-    const bool timed_launches = kt && kt->one_stream;
-    // two streams need two batches of comparable size (render_plan.h two_full)
-    bool dual = !timed_launches && nbatches > 1 &&
-                (K.dual >= 0 ? K.dual == 1 : (!persist && two_full(plan, npix_total, (uint32_t)A.spp)));
-    hipEvent_t ev_start = nullptr, ev_end = nullptr, ev_acc[2] = {nullptr, nullptr};
-    auto release_events = [&] {
-        for (hipEvent_t x : {ev_start, ev_end, ev_acc[0], ev_acc[1]})
-            if (x) (void)hipEventDestroy(x);
-    };
-    if (dual) {
-        if (!wf.twin) wf.twin = new Wavefront();
-        if (!wf.side) e = hipStreamCreateWithFlags(&wf.side, hipStreamNonBlocking);
-        for (hipEvent_t *x : {&ev_start, &ev_end, &ev_acc[0], &ev_acc[1]})
-            if (e == hipSuccess) e = hipEventCreateWithFlags(x, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            if (h_lvl) (void)hipHostFree(h_lvl);
-            release_events();
-            return e;
-        }
-    }
-    hipStream_t st2 = dual ? wf.side : st;
-    // A frame with persistent SDF casts (one stream) runs k_shadow on a stream of its own (BatchSync::aux):
-    // level L's shadow samples overlap level L + 1's march.  SDF_Menger +6.5 %; elsewhere it loses
-    // (bunny on one stream -5 %; beside two batch streams cornell +-0, dragon -1.3 %; profiles/
-    // r03_s18_ab.txt s22, s26).  JSRT_SPLIT=0/1 forces it.
-    const bool split = !timed_launches && ns > 0 && (K.split >= 0 ? K.split == 1 : (persist && !dual));
-    auto aux_of = [&](Wavefront &w) -> hipError_t {
-        hipError_t r = hipSuccess;
-        if (!w.aux) r = hipStreamCreateWithFlags(&w.aux, hipStreamNonBlocking);
-        if (r == hipSuccess && !w.ev_shade) r = hipEventCreateWithFlags(&w.ev_shade, hipEventDisableTiming);
-        if (r == hipSuccess && !w.ev_shadow) r = hipEventCreateWithFlags(&w.ev_shadow, hipEventDisableTiming);
-        return r;
-    };
-    if (split && (e = aux_of(wf)) == hipSuccess && dual) e = aux_of(*wf.twin);
-    if (e != hipSuccess) {
-        if (h_lvl) (void)hipHostFree(h_lvl);
-        release_events();
-        return e;
-    }
-    bool conservative = false, aborted = false;
-    double reported = 0;  // completion already reported: a redone frame reports only beyond it
-    for (int attempt = 0; e == hipSuccess; ++attempt) {
-        if (kt) kt->attempts = (uint32_t)attempt + 1;
-        // chain slots (hybrid: paths + side chains, 256-aligned)
-        const size_t cap = hybrid ? ((paths + paths * wf.pool_factor / 4 + 255) & ~(size_t)255) : paths;
-        if (hybrid && cap * (size_t)depth >= ((size_t)1 << 32)) { e = hipErrorOutOfMemory; break; }  // u32 node index
-        const size_t pool = chain ? cap : paths * wf.pool_factor, level_cap = chain ? cap : pool / 2;
-        int group = 1;
-        // k_shadow: a node's light samples on `group` lanes (one each), or all on one lane (group 1: more than
-        // 64 samples, or JSRT_SHADOW_SERIAL=1, an A/B knob)
-        if (ns > 1 && ns <= 64 && !(K.shadow_serial && !persist))
-            while (group < ns) group *= 2;
-        // hand-off slots: one per node of a level; level 0 holds all `paths` camera rays, the
-        // deeper levels at most level_cap (k_shade poisons the batch before writing past it)
-        const size_t hands = chain ? cap : std::max(level_cap, paths);
-        const size_t shadow = persist ? hands * (size_t)group : 0;
-        auto reserve = [&](Wavefront &w) {
-            return chain ? w.reserve(cap, cap * (size_t)depth, cap, paths, sched, shadow, K)
-                         : w.reserve(pool, pool, hands, paths, SCHED_TREE, shadow, K);
-        };
-        e = reserve(wf);
-        if (e == hipSuccess && dual) {
-            const hipError_t e2 = reserve(*wf.twin);
-            if (e2 == hipErrorOutOfMemory) {  // no room for a second pool: one pool, one stream
-                (void)hipGetLastError();
-                wf.twin->release();
-                dual = false;
-                st2 = st;
-            } else {
-                e = e2;
-            }
-        }
-        if (e != hipSuccess) break;
-        // the frame's settings over a pool's own buffers (every pointer and stride stays the pool's)
-        auto settings = [&](WArgs W) {
-            W.ns = ns;
-            W.group = group;
-            // the node-per-lane k_shadow_node where run_batch's conditions hold (one area light of 2..4 samples in a
-            // flat scene); JSRT_SHADOW_NODE=0/1 forces the lane-per-sample k_shadow / asks for the node form
-            W.shadow_node = K.shadow_node ? 1 : 0;
-            W.chain = chain ? 1 : 0;
-            W.hybrid = hybrid ? 1 : 0;
-            W.cap = (uint32_t)cap;
-            // shadow hand-off bucketed by hit primitive (<= BKT_N buckets of consecutive primitives)
-            int shift = 0;
-            while (S.n_prims > 0 && ((S.n_prims - 1) >> shift) >= BKT_N) ++shift;
-            W.bucket = (learned && !persist && S.n_prims > 0 && ns > 0 && ns <= 64 && K.bucket) ? shift + 1 : 0;
-            W.pool = pool;
-            W.level_cap = level_cap;
-            // children grouped by direction octant where the next cast walks a BVH (A/B on MI355X,
-            // profiles/r03_s3_ab.txt: bunny +5.5 %; cornell -0.8 %, its keyed append costing k_shade 3 ms)
-            W.child_sort = !chain && (K.child_sort >= 0 ? K.child_sort == 1 : ((S.profile & PF_BVH) != 0));  // (tree appends only)
-            // hand-off buckets keyed by the hit point's grid cell, with per-cell shadow-root masks, for flat
-            // scenes (cornell +1.5 %, r03_s15); by hit primitive (runs of consecutive triangles) for meshes,
-            // where the BVH and not the root loop carries the shadow casts (bunny +-0.2 %, r03_s6)
-            const bool grid = K.bucket_grid >= 0 ? K.bucket_grid == 1 : S.profile == PF_ANALYTIC;
-            W.bucket_grid = (W.bucket && S.grid_cells > 0 && grid) ? 1 : 0;
-            W.pixel_major = plan.pixel_major ? 1 : 0;  // the order of a batch's paths (plan_batches)
-            return W;
-        };
-        WArgs W = settings(wf.args);
-        WArgs W2 = dual ? settings(wf.twin->args) : W;  // the twin pool: the same settings over its own buffers
-        if (!feed && (e = hipMemsetAsync(A.accum, 0, (size_t)A.ncols * A.H * 4 * sizeof(float), st)) != hipSuccess) break;
-        if ((e = hipMemsetAsync(W.lvl + LVL_UNDER, 0, 2 * sizeof(uint32_t), st)) != hipSuccess) break;  // frame flags
-        if ((e = hipMemsetAsync(W.fixctr, 0, sizeof(uint32_t), st)) != hipSuccess) break;
-        if (dual && (e = hipMemsetAsync(W2.fixctr, 0, sizeof(uint32_t), st)) != hipSuccess) break;
-        if (dual) {  // the side stream starts after everything enqueued on st so far
-            if ((e = hipEventRecord(ev_start, st)) != hipSuccess || (e = hipStreamWaitEvent(st2, ev_start, 0)) != hipSuccess) break;
-            if ((e = hipMemsetAsync(W2.lvl + LVL_UNDER, 0, 2 * sizeof(uint32_t), st2)) != hipSuccess) break;
-        }
-        // the frame flags (and, for progress, level counts) of both pools, read back after both streams idle
-        auto read_flags = [&]() -> hipError_t {
-            hipError_t r;
-            if (dual && ((r = hipEventRecord(ev_end, st2)) != hipSuccess || (r = hipStreamWaitEvent(st, ev_end, 0)) != hipSuccess))
-                return r;
-            if ((r = hipMemcpyAsync(h_lvl, W.lvl, 64 * sizeof(uint32_t), hipMemcpyDeviceToHost, st)) != hipSuccess) return r;
-            if (dual && (r = hipMemcpyAsync(h_lvl + 64, W2.lvl, 64 * sizeof(uint32_t), hipMemcpyDeviceToHost, st)) != hipSuccess)
-                return r;
-            return hipStreamSynchronize(st);
-        };
-        auto flagged = [&](int k) { return h_lvl[k] != 0 || (dual && h_lvl[64 + k] != 0); };
-        uint64_t bi = 0;  // batch index: even batches on (W, st), odd ones on (W2, st2)
-        auto bounds = [&](uint32_t np) {  // per-level launch bound of a batch of np paths
-            std::vector<size_t> b(depth, 0);
-            if (hybrid) {  // level L: its live chains (<= cap)
-                for (int L = 0; L < A.max_depth; ++L) {
-                    b[L] = L == 0 ? np : cap;
-                    if (L > 0 && !conservative && L < (int)wf.frac.size())  // (at least one block: a launch that
-                        // can set LVL_UNDER for every level chains may continue into, even at a learned count of 0)
-                        b[L] = std::min(cap, std::max<size_t>(256, (size_t)((double)np * wf.frac[L] * margin) + slack));
-                }
-                return b;
-            }
-            size_t ub = np;
-            for (int L = 0; L < A.max_depth && ub > 0; ++L) {
-                b[L] = ub;
-                if (!conservative && L < (int)wf.frac.size())
-                    b[L] = std::min(ub, std::max<size_t>(256, (size_t)((double)np * wf.frac[L] * margin) + slack));
-                ub = L + 1 < A.max_depth ? std::min(ub * (size_t)S.max_children, level_cap) : 0;
-            }
-            return b;
-        };
-        const uint64_t total = (uint64_t)npix_total * A.spp;
-        uint64_t done = 0;
-        // stop: the callback aborted the frame.  redo_now: a progress check found a batch poisoned -- the frame is
-        // redone at once instead of after its last batch, so that every pass is reported exactly once and from a
-        // clean frame (a multi-rank caller keeps its collectives in step on the passes, tiles.render_progressive)
-        bool stop = false, redo_now = false;
-        for (uint32_t row = 0; row < rows && e == hipSuccess && !stop && !redo_now; ++row) {
-            const BatchSpan r0 = batch_span(plan, npix_total, (uint32_t)A.spp, row, 0);
-            const uint32_t s0 = r0.s0, nb = r0.nb;  // the row's samples
-            for (uint32_t col = 0; col < cols; ++col, ++bi) {
-                const BatchSpan span = batch_span(plan, npix_total, (uint32_t)A.spp, row, col);
-                const bool odd = dual && (bi & 1);
-                WArgs &Wb = odd ? W2 : W;
-                const hipStream_t sb = odd ? st2 : st;
-                Wb.p0 = span.p0;
-                Wb.npix = span.npix;
-                Wb.s0 = span.s0;
-                Wb.npaths = span.npix * span.nb;
-                Wb.cap = hybrid ? (uint32_t)cap : Wb.npaths;
-                const std::vector<size_t> bound = learned ? bounds(Wb.npaths) : std::vector<size_t>();
-                BatchSync sync;
-                sync.feed = feed;
-                if (dual) {
-                    sync.wait = bi > 0 ? ev_acc[(bi - 1) & 1] : nullptr;
-                    sync.done = ev_acc[bi & 1];
-                }
-                if (split) {
-                    Wavefront &pw = odd ? *wf.twin : wf;
-                    sync.aux = pw.aux;
-                    sync.shade_done = pw.ev_shade;
-                    sync.shadow_done = pw.ev_shadow;
-                }
-                if (chain) run_batch_pf<true>(S, At, Wb, sb, kt, bound, &sync);
-                else run_batch_pf<false>(S, At, Wb, sb, kt, bound, &sync);
-                if ((e = hipGetLastError()) != hipSuccess) break;
-                done += (uint64_t)Wb.npix * nb;
-                if (kt) ++kt->batches;
-                if (progress && A.kind != JSRT_RENDERER_INCREMENTAL && (!due || due())) {
-                    // Simple / RandomMultisampling report {pass: 0, completion: pixels done / total} from
-                    // inside their pixel loop (renderers.js:28-37): here after a batch, when a callback is
-                    // due (the host's timelimit clock is checked first: no sync otherwise)
-                    if ((e = read_flags()) != hipSuccess) break;
-                    const bool clean = !flagged(LVL_FLAG) && !flagged(LVL_UNDER);
-                    if (!clean) {
-                        redo_now = true;
-                        break;
-                    }
-                    const double c = (double)done / (double)total;
-                    if (c > reported) {
-                        reported = c;
-                        if ((stop = !progress(0, c, clean))) break;
-                    }
-                }
-                if (learned && ((wf.frac.empty() && !conservative) || conservative)) {
-                    // learn the level counts: from the scene's first batch, or -- when that batch was
-                    // not representative and a frame had to be redone -- as the maximum over every
-                    // batch of the conservative redo, so later frames of this shape are not redone
-                    if ((e = hipMemcpyAsync(h_lvl, Wb.lvl, 64 * sizeof(uint32_t), hipMemcpyDeviceToHost, sb)) != hipSuccess) break;
-                    if ((e = hipStreamSynchronize(sb)) != hipSuccess) break;
-                    if (!h_lvl[LVL_FLAG] && !h_lvl[LVL_UNDER]) {
-                        if (wf.frac.size() < (size_t)A.max_depth) wf.frac.assign(A.max_depth, 0.0);
-                        for (int L = 0; L < A.max_depth; ++L)
-                            wf.frac[L] = std::max(wf.frac[L], (double)(hybrid ? h_lvl[2 * L] + h_lvl[2 * L + 1] : h_lvl[L]) / (double)Wb.npaths);
-                    }
-                }
-            }
-            if (e == hipSuccess && progress && A.kind == JSRT_RENDERER_INCREMENTAL && (!due || due())) {  // wait for the pass
-                if ((e = read_flags()) != hipSuccess) break;
-                const bool clean = !flagged(LVL_FLAG) && !flagged(LVL_UNDER);
-                if (!clean) {
-                    redo_now = true;
-                    break;
-                }
-                const double c = (double)done / (double)total;
-                if (c > reported) {
-                    reported = c;
-                    stop = !progress((int)(s0 + nb - 1), c, clean);
-                }
-            }
-        }
-        if (e != hipSuccess) break;
-        if (stop) {  // an aborted frame is not redone (read_flags joins the side stream into st and waits for it)
-            e = read_flags();
-            aborted = true;
-            break;
-        }
-        // The frame flags of both pools, every schedule.  read_flags also joins the side stream into st, so the
-        // caller's stream orders after every batch of the frame (k_final below, and the caller's own work after
-        // jsrt_render_device returns).  A frame that ended with a batch poisoned is redone, never returned: in
-        // the round-4 draft of the hybrid chain this loop broke out for every chain-layout schedule before
-        // reading the flags, so a hybrid frame whose side chains outgrew their slots came back with its
-        // poisoned batches' pixels missing (DESIGN.md §4.1, tests/test_gpu_redo_streams.py).
-        if ((e = read_flags()) != hipSuccess) break;
-        if (!flagged(LVL_FLAG) && !flagged(LVL_UNDER)) break;
-        if (!learned) {  // chain: only k_shade's k_fix_dirs records can run out (fix_record)
-            // both pools take a record per ray slot (the overflow may have been in either); the setting stays for
-            // later frames, like a doubled pool_factor.  A second overflow cannot happen: a level writes at most
-            // one record per ray slot
-            if (wf.fix_all && (!wf.twin || wf.twin->fix_all)) { e = hipErrorOutOfMemory; break; }
-            wf.fix_all = true;
-            if (wf.twin) wf.twin->fix_all = true;
-        } else if (flagged(LVL_FLAG)) {  // a batch outgrew the pool: twice the pool, relearn the counts
-            if (paths * wf.pool_factor > ((size_t)1 << 31) * (hybrid ? 4 : 1)) { e = hipErrorOutOfMemory; break; }
-            wf.pool_factor *= 2;
-            wf.frac.clear();
-        } else {  // a level outgrew its learned bound: redo with the conservative bounds (and relearn)
-            conservative = true;
-            wf.frac.clear();
-        }
-        if (kt) kt->reset();
-    }
-    if (e != hipSuccess && dual) {  // nothing of this frame may still run on the side stream
-        (void)hipStreamSynchronize(st2);
-        (void)hipStreamSynchronize(st);
-    }
-    if (h_lvl) (void)hipHostFree(h_lvl);
-    release_events();
+    bool aborted = false;
+    const hipError_t e = trace_frame(S, A, ns, wf, st, kt, max_paths, progress, due, feed, npix_total, aborted);
     if (e != hipSuccess) return e;
     // an aborted frame leaves the caller's tile as the last preview left it (no k_final over a partial
     // accumulator), with the device idle (read_flags waited): jsrt.h's -4 contract

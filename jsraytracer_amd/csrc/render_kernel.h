@@ -18,6 +18,7 @@ constexpr int BKT_N = 64;           // buckets of the shadow hand-off (hit primi
 constexpr int BKT_S = 16;           // slices per bucket (block index % BKT_S): spreads the counters' atomics
 constexpr int BKT_K = BKT_N * BKT_S;  // counters per level, key = bucket * BKT_S + slice
 constexpr int BKT_LEVEL = 3 * BKT_K + 64;  // words per level: counts, (spare), offsets (+ total)
+constexpr int HAND_PLANES = 6;      // float4 planes of the shadow hand-off (render_levels.h store_hand)
 
 struct RenderArgs {
     int32_t W, H, kind, max_depth;
@@ -134,6 +135,16 @@ struct BatchSync {
     const RayFeed *feed = nullptr;
 };
 
+// What a scene's frames have learned about its tree / hybrid chain batches, per batch shape and schedule
+// (render_plan.h initial_pool_factor, learn_fractions, redo_step): the pool size (tree: x paths; hybrid: paths +
+// paths x pool_factor / 4 chain slots) and the level counts.  Chain: only fix_all.
+struct LearnedPool {
+    size_t pool_paths = 0, pool_factor = 8;
+    int pool_mode = -1;
+    bool fix_all = false;  // k_fix_dirs records for every ray slot (a frame ran out of the default 1/8)
+    std::vector<double> frac;  // level L ray count / paths of the first batch
+};
+
 struct Wavefront {  // owns the batch buffers (cached per scene)
     void *mem = nullptr;
     // The second batch pool and the stream it runs on: consecutive batches alternate between two pools
@@ -143,18 +154,11 @@ struct Wavefront {  // owns the batch buffers (cached per scene)
     // this pool's k_shadow stream and its two ordering events (BatchSync::aux), created on first use
     hipStream_t aux = nullptr;
     hipEvent_t ev_shade = nullptr, ev_shadow = nullptr;
-    // tree / hybrid chain schedule, learned per scene, batch shape and schedule: pool size (tree: x paths;
-    // hybrid: paths + paths x pool_factor / 4 chain slots) and level counts
-    size_t pool_paths = 0, pool_factor = 8;
-    int pool_mode = -1;
-    bool fix_all = false;  // k_fix_dirs records for every ray slot (a frame ran out of the default 1/8)
-    std::vector<double> frac;  // level L ray count / paths of the first batch
+    LearnedPool learned;  // (the twin's: only fix_all is read)
     size_t cap_bytes = 0;
     WArgs args{};
-    // rays: ray slots; nodes: node records; hands: hand-off records; paths: root colours
-    // shadow: light-sample entries of the persistent shadow casts (0 if unused)
-    // mode: 0 chain, 1 tree, 2 hybrid chain; K: the frame's knobs (render.hip)
-    hipError_t reserve(size_t rays, size_t nodes, size_t hands, size_t paths, int mode, size_t shadow, const struct FrameKnobs &K);
+    // sizes the layout of render_plan.h (pool_fields) for d and the frame's knobs, reuses or allocates mem, carves args
+    hipError_t reserve(const struct PoolDims &d, const struct FrameKnobs &K);
     void release();  // frees the buffers (the learned pool / bounds stay)
     ~Wavefront();
 };
@@ -204,8 +208,8 @@ hipError_t color_frame(const DScene &S, const RenderArgs &A, const RayFeed &F, i
 // from the pre-root frame of key (seed, pixel, sample)): W * H x 6 f32.
 hipError_t camera_rays(const DScene &S, const RenderArgs &A, uint32_t sample, float *d_rays, hipStream_t st);
 
-// Device bytes of the batch state per path of a batch (Wavefront::reserve for the schedule and pool
-// render_frame picks for this scene): caps the default batch size.
+// Device bytes of the batch state per path of a batch (render_plan.h pool_bytes_per_path for the schedule
+// this scene's frames run): caps the default batch size.
 size_t wavefront_bytes_per_path(const DScene &S, int ns, int max_depth);
 
 // Running mean of the first `passes` samples -> A.rgba / A.colors (k_final with times(1/passes),

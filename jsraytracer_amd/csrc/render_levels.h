@@ -240,7 +240,6 @@ constexpr uint32_t HAND_DIFF = 0x40000000u;  // plane 2: diff is not the materia
 constexpr uint32_t HAND_R = 0x20000000u;     // plane 3: the specular term needs R
 constexpr uint32_t HAND_SPEC = 0x10000000u;  // plane 4: spec is not the material's constant
 constexpr uint32_t HAND_MAT = 0x0FFFFF00u;   // mat << 8
-constexpr int HAND_PLANES = 6;
 
 // The material data k_shade hands to k_shadow for one lit node (after getBaseFactors), plus the
 // node's RNG frame (its light-sample draws come first, materials.js:244-257).

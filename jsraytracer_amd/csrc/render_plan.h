@@ -1,10 +1,18 @@
-// render_plan.h — the host arithmetic of a frame's batches (render.hip render_frame): the run-time knobs, the
-// shape of the batches, their enumeration, and the pixel order inside them.  No HIP calls: the header builds for
-// the host alone (tests/native/batch_plan_host.hip, tests/test_batch_plan.py).
+// render_plan.h — the host arithmetic of a frame (render.hip run_frame), which the driver only plumbs:
+//   * the run-time knobs (FrameKnobs), the shape of the batches (plan_batches), their enumeration (batch_span,
+//     two_full) and the pixel order inside them (pixel_of);
+//   * the schedule (schedule_of) and, per attempt, the size of a batch pool (initial_pool_factor, pool_shape), the
+//     per-level launch bounds (level_bounds) and the schedule words of a WArgs (batch_settings);
+//   * what a scene learns from its frames (LearnedPool: learn_fractions, redo_step after a poisoned frame);
+//   * the layout of a batch pool, stated once (pool_fields) and visited by a sizer (pool_bytes) and a carver
+//     (carve_pool), with fix_capacity and the per-path estimate that caps the default batch (pool_bytes_per_path).
+// No HIP calls and no getenv: the header builds for the host alone (tests/native/batch_plan_host.hip with
+// tests/test_batch_plan.py, tests/native/frame_policy_host.hip with tests/test_frame_policy.py).
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "render_kernel.h"
 
@@ -138,6 +146,227 @@ __host__ __device__ __forceinline__ bool pixel_of(const RenderArgs &A, uint32_t 
     if (c >= A.ncols || py >= A.H) return false;
     px = owned_to_px(c, A.x_offset, A.x_delt, A.col_block);
     return px < A.W;
+}
+
+// The schedule of a scene's frames: chain when no node can have two children; otherwise the hybrid chain
+// (side chains for second children) for flat scenes, the tree for BVH / SDF scenes (JSRT_HYBRID=0/1 forces
+// one).  A/B on MI355X (profiles/r04_s6_ab.txt): cornell hybrid 493.8 vs tree 466.3 Ms/s; bunny 518.4 vs
+// 555.7, dragon 785.4 vs 792.5, SDF_Menger 112.8 vs 116.1 -- the tree's octant-sorted appends keep BVH
+// casts coherent, and its compaction suits sky-heavy scenes.
+inline int schedule_of(const DScene &S, const FrameKnobs &K) {
+    if (S.max_children <= 1) return SCHED_CHAIN;
+    if (K.hybrid >= 0) return K.hybrid ? SCHED_HYBRID : SCHED_TREE;
+    return S.profile == PF_ANALYTIC ? SCHED_HYBRID : SCHED_TREE;
+}
+constexpr size_t HYBRID_POOL_FACTOR = 2;  // initial hybrid side-chain slots: paths x factor / 4
+
+// The first pool of a batch shape (tree / hybrid chain): a batch of at most 1 M paths starts with 3 side-chain
+// slots per path (a band of columns through a glass sphere outgrows the default 0.5 -- a redo the memory of small
+// batches need not risk)
+inline size_t initial_pool_factor(int sched, size_t paths, const FrameKnobs &K) {
+    if (K.pool_factor) return K.pool_factor;
+    return sched == SCHED_HYBRID ? (paths <= ((size_t)1 << 20) ? 8 : HYBRID_POOL_FACTOR) : 8;
+}
+
+// What Wavefront::reserve lays out.  rays: ray slots; nodes: node records; hands: hand-off records; paths: root
+// colours; mode: SCHED_*; shadow: light-sample entries of the persistent shadow casts (0 if unused)
+struct PoolDims {
+    size_t rays, nodes, hands, paths;
+    int mode;
+    size_t shadow;
+};
+// A batch pool for `paths` paths at one pool factor.  fits: the hybrid chain's u32 node index holds cap x depth.
+struct PoolShape {
+    size_t cap;        // chain slots per level (hybrid: paths + side chains, 256-aligned)
+    size_t pool, level_cap;
+    int group;         // WArgs::group
+    size_t hands, shadow;
+    bool fits;
+    PoolDims dims;
+};
+inline PoolShape pool_shape(int sched, size_t paths, int depth, size_t pool_factor, int ns, bool persist,
+                            const FrameKnobs &K) {
+    const bool hybrid = sched == SCHED_HYBRID, chain = sched != SCHED_TREE;
+    PoolShape P{};
+    P.cap = hybrid ? ((paths + paths * pool_factor / 4 + 255) & ~(size_t)255) : paths;
+    P.fits = !(hybrid && P.cap * (size_t)depth >= ((size_t)1 << 32));
+    P.pool = chain ? P.cap : paths * pool_factor;
+    P.level_cap = chain ? P.cap : P.pool / 2;
+    // k_shadow: a node's light samples on `group` lanes (one each), or all on one lane (group 1: more than
+    // 64 samples, or JSRT_SHADOW_SERIAL=1, an A/B knob)
+    P.group = 1;
+    if (ns > 1 && ns <= 64 && !(K.shadow_serial && !persist))
+        while (P.group < ns) P.group *= 2;
+    // hand-off slots: one per node of a level; level 0 holds all `paths` camera rays, the
+    // deeper levels at most level_cap (k_shade poisons the batch before writing past it)
+    P.hands = chain ? P.cap : std::max(P.level_cap, paths);
+    P.shadow = persist ? P.hands * (size_t)P.group : 0;
+    P.dims = chain ? PoolDims{P.cap, P.cap * (size_t)depth, P.cap, paths, sched, P.shadow}
+                   : PoolDims{P.pool, P.pool, P.hands, paths, SCHED_TREE, P.shadow};
+    return P;
+}
+
+// Per-level launch bound of a batch of np paths (run_batch's `bound`): the most the level can hold, or -- from
+// learned level counts, unless the frame is a conservative redo -- frac[L] x np with JSRT_BOUND_MARGIN and slack.
+inline std::vector<size_t> level_bounds(int sched, uint32_t np, const PoolShape &P, int max_depth, int max_children,
+                                        const std::vector<double> &frac, bool conservative, const FrameKnobs &K) {
+    std::vector<size_t> b(std::max(1, max_depth), 0);
+    auto learned = [&](int L, size_t most) {
+        return std::min(most, std::max<size_t>(256, (size_t)((double)np * frac[L] * K.bound_margin) + K.bound_slack));
+    };
+    if (sched == SCHED_HYBRID) {  // level L: its live chains (<= cap)
+        for (int L = 0; L < max_depth; ++L) {
+            b[L] = L == 0 ? np : P.cap;
+            // (at least one block: a launch that can set LVL_UNDER for every level chains may continue into, even
+            // at a learned count of 0)
+            if (L > 0 && !conservative && L < (int)frac.size()) b[L] = learned(L, P.cap);
+        }
+        return b;
+    }
+    size_t ub = np;
+    for (int L = 0; L < max_depth && ub > 0; ++L) {
+        b[L] = ub;
+        if (!conservative && L < (int)frac.size()) b[L] = learned(L, ub);
+        ub = L + 1 < max_depth ? std::min(ub * (size_t)max_children, P.level_cap) : 0;
+    }
+    return b;
+}
+
+// The frame's settings of a pool's WArgs: the schedule words.  Every pointer and stride stays the pool's.
+inline void batch_settings(WArgs &W, const DScene &S, const FrameKnobs &K, const BatchPlan &plan, const PoolShape &P,
+                           int ns, int sched) {
+    const bool chain = sched != SCHED_TREE;
+    W.ns = ns;
+    W.group = P.group;
+    // the node-per-lane k_shadow_node where run_batch's conditions hold (one area light of 2..4 samples in a
+    // flat scene); JSRT_SHADOW_NODE=0/1 forces the lane-per-sample k_shadow / asks for the node form
+    W.shadow_node = K.shadow_node ? 1 : 0;
+    W.chain = chain ? 1 : 0;
+    W.hybrid = sched == SCHED_HYBRID ? 1 : 0;
+    W.cap = (uint32_t)P.cap;
+    // shadow hand-off bucketed by hit primitive (<= BKT_N buckets of consecutive primitives)
+    int shift = 0;
+    while (S.n_prims > 0 && ((S.n_prims - 1) >> shift) >= BKT_N) ++shift;
+    W.bucket = (sched != SCHED_CHAIN && !plan.persist && S.n_prims > 0 && ns > 0 && ns <= 64 && K.bucket) ? shift + 1 : 0;
+    W.pool = P.pool;
+    W.level_cap = P.level_cap;
+    // children grouped by direction octant where the next cast walks a BVH (A/B on MI355X,
+    // profiles/r03_s3_ab.txt: bunny +5.5 %; cornell -0.8 %, its keyed append costing k_shade 3 ms)
+    W.child_sort = !chain && (K.child_sort >= 0 ? K.child_sort == 1 : ((S.profile & PF_BVH) != 0));  // (tree appends only)
+    // hand-off buckets keyed by the hit point's grid cell, with per-cell shadow-root masks, for flat
+    // scenes (cornell +1.5 %, r03_s15); by hit primitive (runs of consecutive triangles) for meshes,
+    // where the BVH and not the root loop carries the shadow casts (bunny +-0.2 %, r03_s6)
+    const bool grid = K.bucket_grid >= 0 ? K.bucket_grid == 1 : S.profile == PF_ANALYTIC;
+    W.bucket_grid = (W.bucket && S.grid_cells > 0 && grid) ? 1 : 0;
+    W.pixel_major = plan.pixel_major ? 1 : 0;  // the order of a batch's paths (plan_batches)
+}
+
+// Learn the level counts from a batch's read-back lvl words (clean batches only), as the maximum over the batches
+// seen: level L's rays (hybrid: chains continuing into L + side chains started at L) per path of the batch.
+inline void learn_fractions(std::vector<double> &frac, const uint32_t *lvl, int max_depth, bool hybrid, uint32_t npaths) {
+    if (lvl[LVL_FLAG] || lvl[LVL_UNDER]) return;
+    if (frac.size() < (size_t)max_depth) frac.assign(max_depth, 0.0);
+    for (int L = 0; L < max_depth; ++L)
+        frac[L] = std::max(frac[L], (double)(hybrid ? lvl[2 * L] + lvl[2 * L + 1] : lvl[L]) / (double)npaths);
+}
+
+// What follows a poisoned frame (flag: a pool's LVL_FLAG, under: its LVL_UNDER; one of them set): the learned
+// state for the redo, or no larger pool to redo it with.
+enum class Redo { AGAIN, OUT_OF_MEMORY };
+inline Redo redo_step(LearnedPool &st, bool *twin_fix_all, int sched, size_t paths, bool flag, bool under,
+                      bool &conservative) {
+    (void)under;
+    if (sched == SCHED_CHAIN) {  // chain: only k_shade's k_fix_dirs records can run out (fix_record)
+        // both pools take a record per ray slot (the overflow may have been in either); the setting stays for
+        // later frames, like a doubled pool_factor.  A second overflow cannot happen: a level writes at most
+        // one record per ray slot
+        if (st.fix_all && (!twin_fix_all || *twin_fix_all)) return Redo::OUT_OF_MEMORY;
+        st.fix_all = true;
+        if (twin_fix_all) *twin_fix_all = true;
+    } else if (flag) {  // a batch outgrew the pool: twice the pool, relearn the counts
+        if (paths * st.pool_factor > ((size_t)1 << 31) * (sched == SCHED_HYBRID ? 4 : 1)) return Redo::OUT_OF_MEMORY;
+        st.pool_factor *= 2;
+        st.frac.clear();
+    } else {  // a level outgrew its learned bound: redo with the conservative bounds (and relearn)
+        conservative = true;
+        st.frac.clear();
+    }
+    return Redo::AGAIN;
+}
+
+// k_fix_dirs records of a pool.  Unstable spherePicks per level: ~1e-5 of the nodes; every node under
+// JSRT_FORCE_EXACT_PICK, or after a frame that ran out of records (fix_all: the frame is redone with one record
+// per ray slot).  (JSRT_FIX_CAP=n, a test knob: n records until a frame runs out, to exercise the redo on either pool)
+inline size_t fix_capacity(bool fix_all, size_t rays, const FrameKnobs &K) {
+    return fix_all ? rays + 4096 : K.fix_cap >= 0 ? (size_t)K.fix_cap : K.force_exact_pick ? rays + 4096 : rays / 8 + 4096;
+}
+
+// The layout of a batch pool: f(field of w, elements) for every buffer the mode uses, in address order.  Each starts
+// 256-aligned.  The one statement of the layout: pool_bytes sizes it and carve_pool assigns it.
+template <class F>
+inline void pool_fields(WArgs &w, const PoolDims &d, size_t fixcap, F &&f) {
+    const bool tree = d.mode == SCHED_TREE, hybrid = d.mode == SCHED_HYBRID;
+    f(w.ox, d.rays); f(w.oy, d.rays); f(w.oz, d.rays);
+    f(w.dx, d.rays); f(w.dy, d.rays); f(w.dz, d.rays);
+    f(w.addr, d.rays); f(w.key, d.rays);
+    f(w.t, d.rays); f(w.prim, d.rays); f(w.ctx, d.rays);
+    if (tree) f(w.path, d.rays);
+    if (tree || hybrid) f(w.parent, d.rays);
+    if (hybrid) { f(w.list0, d.rays); f(w.list1, d.rays); f(w.endl, d.rays); }  // live lists, last levels
+    f(w.node, d.nodes);
+    f(w.child, 4 * d.nodes);
+    if (tree) f(w.slot, 2 * d.nodes);
+    if (hybrid) f(w.slot, d.nodes);  // (second children)
+    if (tree || hybrid) f(w.root, 3 * d.paths);
+    f(w.hand, HAND_PLANES * d.hands);
+    f(w.hnode, d.hands);
+    f(w.lvl, 64);   // level counts and frame flags
+    f(w.qctr, 64);  // work counters
+    f(w.fixrec, 3 * fixcap);
+    f(w.fixctr, 64);
+    if (d.shadow) { f(w.sray, 2 * d.shadow); f(w.scol, d.shadow); }
+    if (tree || hybrid) {  // buckets
+        f(w.bkt, (size_t)MAX_TREE_DEPTH * BKT_LEVEL);
+        f(w.bbase, (d.hands / 256 + 1) * BKT_N);
+        f(w.brank, d.rays);
+    }
+}
+inline size_t pool_bytes(const PoolDims &d, size_t fixcap) {
+    WArgs w{};
+    size_t bytes = 0;
+    pool_fields(w, d, fixcap, [&](auto *&p, size_t n) { bytes += (n * sizeof(*p) + 255) & ~(size_t)255; });
+    return bytes;
+}
+// w: every buffer of the layout from `base` on (pool_bytes(d, fixcap) bytes), the other pointers null, the strides
+// and fixcap; the rest of w zero
+inline void carve_pool(WArgs &w, const PoolDims &d, size_t fixcap, uint8_t *base) {
+    w = WArgs{};
+    pool_fields(w, d, fixcap, [&](auto *&p, size_t n) {
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base);
+        base += (n * sizeof(*p) + 255) & ~(size_t)255;
+    });
+    w.fixcap = (uint32_t)fixcap;
+    w.nstride = d.nodes;
+    w.hstride = d.hands;
+    w.sstride = d.shadow;
+}
+
+// Device bytes of the batch state per path of a batch on schedule `sched`: an estimate of the layout above at the
+// first pool of a large batch, which caps the default batch size (DESIGN.md §3 sets it beside the real figure).
+inline size_t pool_bytes_per_path(const DScene &S, int ns, int max_depth, int sched) {
+    const size_t ray = 8 * 4 + 8 + 2 * 4, node = 16 + 4 * 16, hand = HAND_PLANES * 16 + 4;
+    const bool persist = (S.profile & PF_SDF) && S.all_roots_prims;
+    size_t group = 1;
+    while ((int)group < ns && ns <= 64) group *= 2;
+    const size_t depth = (size_t)std::max(1, max_depth);
+    if (sched == SCHED_CHAIN)  // chain: one ray and depth nodes per path
+        return ray + depth * node + hand + (persist ? group * 48 : 0);
+    if (sched == SCHED_HYBRID)  // per chain slot: ray + parent + rank, depth x (node + second-child slot), hand-off
+        return (4 + HYBRID_POOL_FACTOR) * (ray + 17 + depth * (node + 16) + hand + (persist ? group * 48 : 0) +
+                                           BKT_N * 4 / 256) / 4 + 12;
+    const size_t pool = 8, level_cap = pool / 2;  // pool_shape: pool = 8 x paths, level_cap = pool / 2
+    // + the bucketed hand-off's ranks (4 B per pool slot) and block bases (BKT_N words per 256 hand-off slots)
+    return pool * (ray + 8 + node + 2 * 16 + 4) + level_cap * (hand + (persist ? group * 48 : 0) + BKT_N * 4 / 256) + 12;
 }
 
 }  // namespace jsrt
