@@ -115,7 +115,8 @@ def scene_header(blob):
 
 
 # ---- golden fixtures (generated from the reference by oracle/refharness/regen_goldens.sh) ----
-# `sub`: a fixture tree of the same layout below tests/golden ("sdfzoo": oracle/refharness/regen_zoo.sh)
+# `sub`: a fixture tree of the same layout below tests/golden ("sdfzoo": oracle/refharness/regen_zoo.sh; "frames":
+# regen_frames.sh, images and index only -- its scenes are those of tests/golden/scenes)
 def _golden(sub, *parts):
     return os.path.join(GOLDEN, sub, *parts) if sub else os.path.join(GOLDEN, *parts)
 

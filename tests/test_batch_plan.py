@@ -164,3 +164,77 @@ def test_pixel_of_is_a_bijection_onto_the_patch_grid(lib, tile_p):
                 assert np.array_equal(py % 8, np.tile(np.arange(64) // 8, pxn * pyn))
                 if tile_p == 0:
                     assert np.array_equal((py // 8) * pxn + c // 8, np.repeat(np.arange(pxn * pyn), 64))  # raster patches
+
+
+# ---- the smallest and the odd frames (tests/test_gpu_frames.py renders them) ------------------------------------
+def _plan_of(lib, profile, patches, spp, max_paths=2**25, split_min=22, persist=0):
+    r = np.array([(profile, 1, patches, spp, 0, 1, max_paths, -1, 256, 8, persist, 1, split_min, 1)], np.int64)
+    npix, nsb, pixel_major, tile_p, per, split_pixels, split, two, rows, cols = (int(x) for x in _plans(lib, r)[0])
+    return dict(npix=npix, nsb=nsb, pixel_major=pixel_major, split=split, two_full=two, rows=rows, cols=cols)
+
+
+def test_plans_of_one_patch_and_odd_frames(lib):
+    """1 x 1 and 1 x 7 (one patch of 64 pixels, 1 or 7 of them in the image), 37 x 23 (15 patches) and 9 x 65 (18):
+    one batch of every patch and sample by default; under JSRT_SPLIT_MIN=8 a one-patch frame of 3 samples (192 paths)
+    stays whole while 15 and 18 patches split -- 8 + 7 and 9 + 9 patches pixel-major, 2 + 1 samples sample-major."""
+    for profile, patches, spp in itertools.product(PROFILES, (1, 15, 18), (1, 2, 3)):
+        p = _plan_of(lib, profile, patches, spp)
+        assert (p["npix"], p["nsb"], p["rows"], p["cols"], p["split"]) == (patches * 64, spp, 1, 1, 0), (profile, patches, spp)
+        assert p["pixel_major"] == (profile != PF_ANALYTIC)
+    for profile, spp in itertools.product(PROFILES, (1, 2, 3)):
+        p = _plan_of(lib, profile, 1, spp, split_min=8)
+        assert (p["npix"], p["nsb"], p["rows"], p["cols"], p["split"]) == (64, spp, 1, 1, 0), (profile, spp)
+    for patches, first in ((15, 8), (18, 9)):
+        for spp in (2, 3):
+            p = _plan_of(lib, PF_SDF, patches, spp, split_min=8)  # pixel-major: pixel halves
+            assert (p["npix"], p["nsb"], p["rows"], p["cols"], p["split"], p["two_full"]) == (first * 64, spp, 1, 2, 1, 1)
+            p = _plan_of(lib, PF_ANALYTIC, patches, spp, split_min=8)  # sample-major: sample halves
+            assert (p["npix"], p["nsb"], p["rows"], p["cols"], p["split"], p["two_full"]) == (patches * 64, (spp + 1) // 2, 2, 1, 1, 1)
+        for profile in PROFILES:  # one sample (SimpleRenderer), or persistent casts: never split
+            assert _plan_of(lib, profile, patches, 1, split_min=8)["split"] == 0
+        assert _plan_of(lib, PF_SDF, patches, 3, split_min=8, persist=1)["split"] == 0
+    # the 20 x 12 ladder frame (6 patches, 2 samples) at max_paths 128: six batches in either path order
+    p = _plan_of(lib, PF_ANALYTIC, 6, 2, max_paths=128)
+    assert (p["npix"], p["nsb"], p["rows"], p["cols"]) == (128, 1, 2, 3)
+    p = _plan_of(lib, PF_SDF, 6, 2, max_paths=128)
+    assert (p["npix"], p["nsb"], p["rows"], p["cols"]) == (64, 2, 1, 6)
+    # a batch is never smaller than one patch, however small max_paths
+    p = _plan_of(lib, PF_ANALYTIC, 1, 3, max_paths=1)
+    assert (p["npix"], p["nsb"], p["rows"], p["cols"]) == (64, 1, 3, 1)
+
+
+def _pixels(lib, W, H, ncols, x_offset, x_delt, col_block, tile_p):
+    n = ((ncols + 7) // 8) * ((H + 7) // 8) * 64
+    out = np.empty((n, 4), np.int32)
+    lib.pixels(W, H, ncols, x_offset, x_delt, col_block, tile_p, out.ctypes.data)
+    return out
+
+
+@pytest.mark.parametrize("tile_p", [0, 8])
+def test_pixel_of_on_frames_below_a_patch(lib, tile_p):
+    """The valid indices of a frame are its pixels, each once: 1 x 1 (index 0 of 64), 1 x 7 (a column: indices 0, 8,
+    ... 48), 13 x 1 (a row over two patches), 37 x 23 and 9 x 65 (partial last patch row and column), one worker's
+    columns (x_offset 2, x_delt 5 of 37: 7 columns), a column per worker (x_delt = W), a block-cyclic rank whose last
+    block is partial (W = 37, col_block 8, rank 1 of 3: 8 + 5 columns) and no owned column at all."""
+    def image_pixels(W, H, ncols, x_offset, x_delt, col_block=1):
+        out = _pixels(lib, W, H, ncols, x_offset, x_delt, col_block, tile_p)
+        v = out[out[:, 3] == 1]
+        assert len(out) == ((ncols + 7) // 8) * ((H + 7) // 8) * 64
+        return out, sorted((int(px), int(py)) for _, py, px, _ in v)
+    out, px = image_pixels(1, 1, 1, 0, 1)
+    assert px == [(0, 0)] and out[0, 3] == 1 and len(out) == 64
+    out, px = image_pixels(1, 7, 1, 0, 1)
+    assert px == [(0, y) for y in range(7)] and list(np.flatnonzero(out[:, 3])) == [8 * y for y in range(7)]
+    out, px = image_pixels(13, 1, 13, 0, 1)
+    assert px == [(x, 0) for x in range(13)] and len(out) == 128
+    for W, H in ((37, 23), (9, 65), (7, 9), (13, 7)):
+        out, px = image_pixels(W, H, W, 0, 1)
+        assert px == [(x, y) for x in range(W) for y in range(H)], (W, H)
+    out, px = image_pixels(37, 23, 7, 2, 5)
+    assert px == [(x, y) for x in range(2, 37, 5) for y in range(23)] and len(out) == 3 * 64
+    for k in (0, 12):
+        out, px = image_pixels(13, 7, 1, k, 13)
+        assert px == [(k, y) for y in range(7)]
+    out, px = image_pixels(37, 23, 13, 1, 3, 8)
+    assert px == [(x, y) for x in list(range(8, 16)) + list(range(32, 37)) for y in range(23)]
+    assert len(_pixels(lib, 5, 23, 0, 1, 3, 8, tile_p)) == 0  # no owned column: no patch, no index

@@ -287,6 +287,98 @@ def test_learn_fractions(lib):
         assert learn([1.0, 0.25], {0: 1000, 1: 500, flag: 1}, 2, 0, 1000) == [1.0, 0.25]
 
 
+# ---- the depth limits: maxRecursionDepth 1 and MAX_TREE_DEPTH ---------------------------------------------------
+def test_level_bounds_at_depth_1_and_16(lib):
+    """One level: a single entry, the batch's paths.  Sixteen: sixteen entries, the last one from frac[15] (learned) or
+    the level's most (conservative) -- a table one entry short, or a loop that stops at 15, shows here alone."""
+    for sched, frac, conservative in itertools.product((TREE, HYBRID), ([], [1.0], [1.0] + [0.5] * 15), (0, 1)):
+        assert _bounds(lib, sched, 768, 768, 1, 8, 2, frac, conservative, 1.25, 4096) == [768], (sched, frac, conservative)
+    np_ = 100000
+    frac = [1.0] + [(L + 1) / 100 for L in range(1, MAX_TREE_DEPTH)]  # a value per level: 2 %, 3 %, ... 16 %
+    want = [np_] + [1000 * (L + 1) for L in range(1, MAX_TREE_DEPTH)]
+    for sched in (TREE, HYBRID):
+        assert _bounds(lib, sched, np_, np_, 16, 8, 2, frac, 0, 1.0, 0) == want, sched
+        assert _bounds(lib, sched, np_, np_, 16, 8, 2, frac + [0.9, 0.9], 0, 1.0, 0) == want, sched  # no 17th level
+    # conservative: the hybrid chain's 15 deeper levels may hold every chain slot; the tree's double up to level_cap
+    cap, pool, level_cap = was_shape(HYBRID, 768, 16, 8, 0, 0, 0)[:3]
+    assert cap == 2304 and _bounds(lib, HYBRID, 768, 768, 16, 8, 2, [], 0, 1.25, 4096) == [768] + [cap] * 15
+    cap, pool, level_cap = was_shape(TREE, 768, 16, 8, 0, 0, 0)[:3]
+    assert level_cap == 3072
+    assert _bounds(lib, TREE, 768, 768, 16, 8, 2, [], 0, 1.25, 4096) == [768, 1536] + [3072] * 14
+    assert _bounds(lib, TREE, 768, 768, 16, 8, 1, [], 0, 1.25, 4096) == [768] * 16
+    # counts learned by a frame of depth 8 bound the first 8 levels of a frame of depth 16, the rest are conservative
+    got = _bounds(lib, HYBRID, np_, np_, 16, 8, 2, frac[:8], 0, 1.0, 0)
+    assert got[:8] == want[:8] and got[8:] == [was_shape(HYBRID, np_, 16, 8, 0, 0, 0)[0]] * 8
+
+
+def test_learn_fractions_at_depth_1_and_16(lib):
+    def learn(frac, lvl, max_depth, hybrid, npaths):
+        f = np.zeros(max(len(frac), max_depth), np.float64)
+        f[:len(frac)] = frac
+        lv = np.zeros(64, np.uint32)
+        for k, v in lvl.items():
+            lv[k] = v
+        n = lib.learn(f.ctypes.data, len(frac), lv.ctypes.data, max_depth, hybrid, npaths)
+        return list(f[:n])
+    # one level: one entry, whatever the words beyond it hold
+    assert learn([], {0: 1000, 1: 7, 2: 7}, 1, 0, 1000) == [1.0]
+    assert learn([], {0: 1000, 1: 0, 2: 7, 3: 7}, 1, 1, 1000) == [1.0]
+    assert learn([0.5], {0: 250}, 1, 0, 1000) == [0.5]
+    # sixteen levels: lvl[15] (tree), the pair lvl[30, 31] (hybrid chain) are the last words read -- below the frame
+    # flags lvl[62, 63] -- and the words after them are not
+    tree = {L: 1000 - 50 * L for L in range(MAX_TREE_DEPTH)}
+    assert learn([], {**tree, 16: 999999}, 16, 0, 1000) == [(1000 - 50 * L) / 1000 for L in range(16)]
+    pairs = {}
+    for L in range(MAX_TREE_DEPTH):
+        pairs[2 * L], pairs[2 * L + 1] = 800 - 40 * L, 3 * L
+    assert 2 * (MAX_TREE_DEPTH - 1) + 1 < LVL_UNDER
+    want = [(800 - 40 * L + 3 * L) / 1000 for L in range(16)]
+    assert want[15] == (200 + 45) / 1000
+    assert learn([], {**pairs, 32: 999999, 33: 999999}, 16, 1, 1000) == want
+    assert learn([1.0] * 16, pairs, 16, 1, 1000) == [1.0] * 16  # the maximum over batches, level by level
+    for flag in (LVL_FLAG, LVL_UNDER):
+        assert learn([], {**pairs, flag: 1}, 16, 1, 1000) == []
+
+
+# the batches of the thumbnail frames of tests/test_gpu_frames.py: (patches, spp) of 1 x 1 and 1 x 7 (one patch),
+# 20 x 12 (6), 37 x 23 (15) and 9 x 65 (18 patches)
+FRAMES = [(1, 1), (1, 3), (6, 2), (15, 1), (15, 3), (18, 3)]
+
+
+def test_pool_carve_of_the_smallest_frames(lib):
+    """A one-patch batch at depths 1 and 16, and the thumbnails' batches, on every schedule and at the first pool
+    factors a frame can start from: the pool holds the tables the depth indexes -- depth x cap node records (chain
+    layouts), MAX_TREE_DEPTH bucket levels, 64 level words -- disjoint, within its size."""
+    for (patches, spp), depth, sched, factor in itertools.product(FRAMES, (1, 16), (CHAIN, TREE, HYBRID), (1, 8)):
+        paths = patches * 64 * spp
+        shp = _shape(lib, sched, paths, depth, factor, 4, 0, 0)
+        assert shp == was_shape(sched, paths, depth, factor, 4, 0, 0)
+        cap, pool, level_cap, group, hands, shadow, fits = shp[:7]
+        dims = shp[7:]
+        head, off, size = np.empty(7, np.int64), np.empty(31, np.int64), np.empty(31, np.int64)
+        lib.layout(_ll(*dims).ctypes.data, 0, _ll(*KNOBS0).ctypes.data, head.ctypes.data, off.ctypes.data, size.ctypes.data)
+        case = (patches, spp, depth, sched, factor)
+        at = {NAMES[i]: (int(off[i]), int(size[i])) for i in range(31) if off[i] >= 0}
+        assert fits and cap >= paths, case
+        if sched == TREE:
+            assert at["node"][1] == 16 * pool and at["slot"][1] == 2 * 16 * pool and pool == paths * factor, case
+        else:
+            assert at["node"][1] == 16 * cap * depth and at["child"][1] == 4 * 16 * cap * depth, case  # node [L * cap + slot]
+            assert int(head[3]) == cap * depth, case  # nstride
+        if sched == HYBRID:
+            assert at["slot"][1] == 16 * cap * depth and at["endl"][1] == cap and cap % 256 == 0, case
+        if sched != CHAIN:
+            assert at["bkt"][1] == 4 * MAX_TREE_DEPTH * BKT_LEVEL and at["root"][1] == 4 * 3 * paths, case
+        assert at["lvl"][1] == 4 * 64 and at["qctr"][1] == 4 * 64, case
+        assert 2 * depth <= LVL_UNDER and 32 + depth <= 64, case  # count pairs below the flags; qctr [L], [32 + L]
+        spans = sorted(at.values())
+        assert all(o + s <= o2 for (o, s), (o2, _) in zip(spans, spans[1:])), case
+        assert spans[-1][0] + spans[-1][1] <= int(head[0]), case
+        # the launch bounds of such a batch never ask a level for more than the pool gives it
+        b = _bounds(lib, sched, paths, paths, depth, factor, 2, [], 1, 1.25, 4096) if sched != CHAIN else []
+        assert len(b) == (depth if sched != CHAIN else 0) and all(x <= (cap if sched == HYBRID else max(paths, level_cap)) for x in b), case
+
+
 # ---- redo_step --------------------------------------------------------------------------------------------------
 def _redo(lib, factor, fix_all, twin, twin_fix, nfrac, conservative, sched, paths, flag, under):
     st = _ll(factor, fix_all, twin, twin_fix, nfrac, conservative)
