@@ -70,6 +70,16 @@ class ColorParams(ctypes.Structure):  # jsrt_color_params
                 ("spp", ctypes.c_int32), ("max_paths", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
+# exported symbols of include/jsrt_views.h (many cameras of one scene in one call)
+VIEWS_EXPORTS = ["jsrt_scene_camera", "jsrt_render_views", "jsrt_render_views_device"]
+
+
+class CameraRec(ctypes.Structure):  # jsrt_camera: the fields of jsrt_scene.h's CAMR record
+    _fields_ = [("kind", ctypes.c_int32), ("pad", ctypes.c_int32), ("transform", ctypes.c_double * 16),
+                ("tan_fov", ctypes.c_double), ("aspect", ctypes.c_double), ("focus_distance", ctypes.c_double),
+                ("sensor_size", ctypes.c_double)]
+
+
 class MeshOptions(ctypes.Structure):
     _fields_ = [("bvh_object", ctypes.c_int32), ("pad", ctypes.c_int32), ("min_area", ctypes.c_double)]
 
@@ -223,6 +233,24 @@ def color_api():
                                     ctypes.POINTER(ColorParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Stats)]
     L.jsrt_camera_rays.restype = ctypes.c_int
     L.jsrt_camera_rays.argtypes = [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_uint32, ctypes.c_void_p]
+    return L
+
+
+def views_api():
+    """The library with the jsrt_views.h entry points bound (JsrtError if it lacks them); bound where they are
+    called, as the texture entry points are."""
+    L = lib()
+    if not all(hasattr(L, n) for n in VIEWS_EXPORTS):
+        raise JsrtError(f"{LIB_PATH} has no jsrt_views entry points: rebuild it")
+    L.jsrt_scene_camera.restype = ctypes.c_int
+    L.jsrt_scene_camera.argtypes = [ctypes.c_void_p, ctypes.POINTER(CameraRec)]
+    L.jsrt_render_views.restype = ctypes.c_int
+    L.jsrt_render_views.argtypes = [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p, ctypes.c_int32,
+                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(Stats)]
+    L.jsrt_render_views_device.restype = ctypes.c_int
+    L.jsrt_render_views_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(Params), ctypes.c_void_p, ctypes.c_int32,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.POINTER(Stats)]
     return L
 
 

@@ -25,13 +25,14 @@ FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-ffp-contract=off", "-f
          "-Wall", "-Wno-unused-function"]
 
 INCLUDE = os.path.join(HERE, "..", "include")
-PUBLIC = ["jsrt.h", "jsrt_scene.h", "jsrt_mesh.h", "jsrt_json.h", "jsrt_texture.h", "jsrt_color.h"]
+PUBLIC = ["jsrt.h", "jsrt_scene.h", "jsrt_mesh.h", "jsrt_json.h", "jsrt_texture.h", "jsrt_color.h", "jsrt_views.h"]
 # objects: (object stem, source, extra defines, dependencies); an object is rebuilt only when these change
-UNITS = [("render", "render.hip", [], HEADERS + ["jsrt.h", "jsrt_scene.h"])]
+UNITS = [("render", "render.hip", [], HEADERS + ["jsrt.h", "jsrt_scene.h"]),
+         ("render_views", "render_views.hip", [], HEADERS + ["jsrt.h", "jsrt_scene.h"])]  # jsrt_views.h: k_gen_views, k_fold_views
 # each profile in three parts (render_pf.hip JSRT_PART: chain kernels, tree kernels, single-cast entries)
 UNITS += [(f"render_pf{pf}_{part}", "render_pf.hip", [f"-DJSRT_PF={pf}", f"-DJSRT_PART={part}"],
            HEADERS + ["jsrt.h", "jsrt_scene.h"]) for pf in PROFILES.values() for part in range(3)]
-UNITS += [("capi", "capi.cpp", [], HEADERS + ["jsrt.h", "jsrt_scene.h", "jsrt_color.h"]),
+UNITS += [("capi", "capi.cpp", [], HEADERS + ["jsrt.h", "jsrt_scene.h", "jsrt_color.h", "jsrt_views.h"]),
           ("scene_load", "scene_load.cpp", [], HEADERS + ["jsrt.h", "jsrt_scene.h"]),
           ("mesh_build", "mesh_build.cpp", [], ["jsrt_mesh.h", "jsrt_scene.h", "obj_parse.h"]),
           ("json_scene", "json_scene.cpp", [], ["jsrt_json.h", "jsrt_scene.h", "obj_parse.h"]),

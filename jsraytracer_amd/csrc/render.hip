@@ -833,7 +833,7 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
 hipError_t color_frame(const DScene &S, const RenderArgs &A, const RayFeed &F, int ns, Wavefront &wf, hipStream_t st,
                        KernelTimes *kt, size_t max_paths) {
     if (F.n == 0 || F.spp == 0) return hipSuccess;
-    if (!F.rays || !F.out || A.max_depth < 0 || A.max_depth > MAX_TREE_DEPTH) return hipErrorInvalidValue;
+    if ((!F.rays && !F.cams) || !F.out || A.max_depth < 0 || A.max_depth > MAX_TREE_DEPTH) return hipErrorInvalidValue;
     if (A.max_depth == 0)  // World.color(ray, 0) = black (world.js:32): nothing is traced
         return hipMemsetAsync(F.out, 0, (size_t)F.n * F.spp * 3 * sizeof(float), st);
     RenderArgs Ar{};  // what the plan and the kernels after the first read of a frame: the batch grid, depth and seed
@@ -841,6 +841,11 @@ hipError_t color_frame(const DScene &S, const RenderArgs &A, const RayFeed &F, i
     Ar.seed = A.seed;
     Ar.spp = (int32_t)F.spp;
     Ar.kind = JSRT_RENDERER_RANDOM;  // (no pass structure: nothing is reported)
+    if (F.cams) {  // a view batch: the frame size and the renderer kind (its jitter), as k_gen reads them
+        Ar.W = A.W;
+        Ar.H = A.H;
+        Ar.kind = A.kind;
+    }
     Ar.patches = (int32_t)(((uint64_t)F.n + 63) / 64);  // the plan's pixel count, in whole 64s
     return run_frame(S, Ar, ns, wf, st, kt, max_paths, nullptr, nullptr, &F);
 }

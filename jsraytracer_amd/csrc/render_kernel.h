@@ -114,11 +114,17 @@ struct WArgs {
 // frame's batches take their level-0 rays from (k_gen_rays) and where their paths' colours go (k_store_colors).
 // A batch is rays [W.p0, W.p0 + W.npix) x samples [W.s0, W.s0 + npaths / npix), a ray's samples side by side
 // (W.pixel_major is not read).
+// A view batch (views_frame, jsrt_views.h): cams is set, rays and keys are null, and item i of the feed is pixel
+// (item0 + i) % view_px of view (item0 + i) / view_px, whose level-0 ray k_gen_views computes from cams[view] with
+// the frame's own key (seed of the view, pixel, sample) and pre-root draws.
 struct RayFeed {
     const float *rays;     // n x 6 f32: origin xyz (w = 1), direction xyz (w = 0)
     const uint32_t *keys;  // n: the "pixel" of a ray's RNG key (nullable: the ray's index)
     float *out;            // n x spp x 3 f32: World.color of (ray, sample)
     uint32_t n, spp, sample0;
+    const DCamera *cams;    // nviews cameras (null: the caller's rays, above)
+    const uint32_t *seeds;  // nviews seeds (nullable: the frame's seed for every view)
+    uint32_t nviews, view_px, item0;  // views, pixels per view (W x H), the feed's first item among nviews x view_px
 };
 
 // Accumulation order across the two batch streams (render_frame): the batch's k_accum / k_resolve waits
@@ -201,8 +207,15 @@ hipError_t render_frame(const DScene &S, const RenderArgs &A, int ns, Wavefront 
                         const std::function<bool()> &due = nullptr);
 
 // World.color(ray, A.max_depth) of F.n rays x F.spp samples (device buffers) through the frame's batches, level
-// loop, pools, streams and redo logic: of A only max_depth (>= 1) and seed are read.
+// loop, pools, streams and redo logic: of A only max_depth (>= 1) and seed are read (a view batch, F.cams: W, H and
+// kind too, which k_gen_views reads as k_gen does).
 hipError_t color_frame(const DScene &S, const RenderArgs &A, const RayFeed &F, int ns, Wavefront &wf, hipStream_t st,
+                       KernelTimes *kt, size_t max_paths);
+// F.nviews frames of A's W x H, spp, kind and max_depth, view v through F.cams[v] with seed F.seeds[v] (null: A.seed),
+// into A.rgba / A.colors (nullable) as nviews x H x W row-major frames (render_views.hip, jsrt_views.h): view v is
+// bit for bit the frame render_frame gives a scene whose camera is F.cams[v].  The views' pixels are the items of
+// feed frames (color_frame) of at most max_paths paths each; of F only cams, seeds and nviews are read.
+hipError_t views_frame(const DScene &S, const RenderArgs &A, const RayFeed &F, int ns, Wavefront &wf, hipStream_t st,
                        KernelTimes *kt, size_t max_paths);
 // The ray k_gen starts for every pixel py * W + px of A's W x H and sample index `sample` (jitter and DOF draws
 // from the pre-root frame of key (seed, pixel, sample)): W * H x 6 f32.

@@ -668,6 +668,8 @@ __global__ __launch_bounds__(256) void k_resolve_paths(RenderArgs A, WArgs W);
 // a batch of the caller's rays (RayFeed): k_gen's and k_accum / k_resolve's twins
 __global__ __launch_bounds__(256) void k_gen_rays(RenderArgs A, WArgs W, RayFeed F);
 __global__ __launch_bounds__(256) void k_store_colors(RenderArgs A, WArgs W, RayFeed F);
+// a view batch (RayFeed::cams, render_views.hip): the level-0 rays of the views' pixels, in k_gen_rays's place
+__global__ __launch_bounds__(256) void k_gen_views(RenderArgs A, WArgs W, RayFeed F);
 
 // Grid of a persistent kernel: as many 256-thread blocks as the device keeps resident (occupancy x
 // CUs), never more than the work needs (render.hip).
@@ -1594,7 +1596,8 @@ void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t
     if (W.bucket) (void)hipMemsetAsync(W.bkt, 0, (size_t)MAX_TREE_DEPTH * BKT_LEVEL * sizeof(uint32_t), st);
     const RayFeed *feed = sync ? sync->feed : nullptr;  // the caller's rays in the camera's place
     timed(KT_GEN, [&] {
-        if (feed) hipLaunchKernelGGL(k_gen_rays, dim3(grid(W.npaths)), dim3(256), 0, st, A, W, *feed);
+        if (feed && feed->cams) hipLaunchKernelGGL(k_gen_views, dim3(grid(W.npaths)), dim3(256), 0, st, A, W, *feed);
+        else if (feed) hipLaunchKernelGGL(k_gen_rays, dim3(grid(W.npaths)), dim3(256), 0, st, A, W, *feed);
         else hipLaunchKernelGGL(k_gen, dim3(grid(W.npaths)), dim3(256), 0, st, S, A, W);
     });
     // the batch's colours: into the frame's accumulator per pixel, or each path's own to the caller (k_store_colors)
@@ -1688,6 +1691,13 @@ void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t
     if (split && W.ns > 0 && !ubs.empty()) (void)hipStreamWaitEvent(st, sync->shadow_done, 0);  // the lit colours
     if (CHAIN && W.hybrid) {  // side chains deepest start first, then the paths; k_accum adds them in sample order
         timed(KT_RESOLVE, [&] {
+            if (ubs.empty()) {
+                // maxRecursionDepth 0 (a blob's own: jsrt_params cannot ask for it): no level ran, so no chain has a
+                // last level and W.endl, which resolve_chain starts from, is unwritten pool memory.  World.color(ray, 0)
+                // is black (world.js:32): the root colours are cleared instead of resolved.
+                (void)hipMemsetAsync(W.root, 0, (size_t)W.npaths * 3 * sizeof(float), st);
+                return;
+            }
             for (int s = (int)ubs.size() - 1; s >= 1; --s)  // (the chains started at s are live at s: <= ubs[s])
                 hipLaunchKernelGGL(k_resolve_side, dim3(grid_ub(ubs[s])), dim3(256), 0, st, A, W, s);
             hipLaunchKernelGGL(k_resolve_paths, dim3(grid(W.npaths)), dim3(256), 0, st, A, W);

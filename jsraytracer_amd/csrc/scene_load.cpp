@@ -1069,14 +1069,8 @@ struct Loader {
         S.height = (int32_t)R.height;
         if (R.bg_len != 3) fail("World.bg_color must be a 3-vector");
         memcpy(S.bg, R.bg, sizeof S.bg);
-        const jsrt_rec_camera &C = *B.cam;
-        if (!is_affine(C.transform)) fail("non-affine camera transform");
-        memcpy(S.cam.T, C.transform, sizeof S.cam.T);
-        S.cam.tan_fov = C.tan_fov;
-        S.cam.aspect = C.aspect;
-        S.cam.focus = C.focus_distance;
-        S.cam.sensor = C.sensor_size;
-        S.cam.kind = (int32_t)C.kind;
+        std::string cam_err;
+        if (camera_from_record(*B.cam, S.cam, cam_err)) fail(cam_err);
 
         // the shadow hand-off packs the material index into 20 bits beside the grid mask and its plane flags
         // (render_levels.h store_hand: mat << 8 | mask | HAND_*)
@@ -1379,6 +1373,21 @@ struct Loader {
 };
 
 }  // namespace
+
+int camera_from_record(const jsrt_rec_camera &C, DCamera &cam, std::string &err) {
+    if (!is_affine(C.transform)) {
+        err = "non-affine camera transform";
+        return -1;
+    }
+    cam = DCamera();
+    memcpy(cam.T, C.transform, sizeof cam.T);
+    cam.tan_fov = C.tan_fov;
+    cam.aspect = C.aspect;
+    cam.focus = C.focus_distance;
+    cam.sensor = C.sensor_size;
+    cam.kind = (int32_t)C.kind;
+    return 0;
+}
 
 int load_scene(const void *blob, size_t nbytes, HostScene &out, std::string &err) {
     try {

@@ -61,6 +61,10 @@ struct HostScene {
     int32_t grid_dim[3] = {0, 0, 0}, grid_cells = 0;
 };
 
+// The device camera of a CAMR record (the loader's own step, and jsrt_views.h's per view): 0, or -1 and err for a
+// transform the kernels cannot carry (row 3 must be 0, 0, 0, 1).
+int camera_from_record(const jsrt_rec_camera &C, DCamera &cam, std::string &err);
+
 // Returns 0 on success; otherwise fills err.
 int load_scene(const void *blob, size_t nbytes, HostScene &out, std::string &err);
 

@@ -51,6 +51,94 @@ class PixelBuffer:
         return self.imgdata[y, x].astype(np.float64) / 255
 
 
+CAMERA_PERSPECTIVE, CAMERA_DOF = 0, 1  # include/jsrt_scene.h JSRT_CAMERA_*
+_CAMR = 0x524D4143  # 'CAMR'
+_CAMR_FMT = "<II16d4d"  # jsrt_rec_camera: kind, pad, transform (Mat rows), tan_fov, aspect, focus_distance, sensor_size
+
+
+class Camera:
+    """The camera of one view (include/jsrt_views.h jsrt_camera; cameras.js:18-53 as the render path reads it): kind
+    (CAMERA_PERSPECTIVE / CAMERA_DOF), transform (4 x 4 float64, Mat rows; row 3 must be 0, 0, 0, 1), tan_fov, aspect,
+    and for CAMERA_DOF focus_distance and sensor_size.  It holds tan_fov, not the field of view: the reference keeps
+    Math.tan(fov / 2) as V8 computed it, and a frame is bit-exact only with that double."""
+
+    def __init__(self, transform, tan_fov, aspect, kind=CAMERA_PERSPECTIVE, focus_distance=0.0, sensor_size=0.0):
+        self.transform = np.array(transform, np.float64).reshape(4, 4)
+        self.tan_fov, self.aspect = float(tan_fov), float(aspect)
+        self.kind = int(kind)
+        self.focus_distance, self.sensor_size = float(focus_distance), float(sensor_size)
+
+    @classmethod
+    def from_fov(cls, fov, aspect, transform, kind=CAMERA_PERSPECTIVE, focus_distance=0.0, sensor_size=0.0):
+        """PerspectiveCamera(fov, aspect, transform) with tan_fov = math.tan(fov / 2).  That is the C library's tan,
+        not pinned to V8's Math.tan: the two may differ in the last bit.  Where a frame must match the reference bit
+        for bit, pass the reference's own tan_fov to Camera(...) instead."""
+        import math
+        return cls(transform, math.tan(fov / 2), aspect, kind, focus_distance, sensor_size)
+
+    def replace(self, **kw):
+        """A copy with some fields replaced."""
+        d = dict(transform=self.transform, tan_fov=self.tan_fov, aspect=self.aspect, kind=self.kind,
+                 focus_distance=self.focus_distance, sensor_size=self.sensor_size)
+        d.update(kw)
+        return Camera(**d)
+
+    def _rec(self):
+        t = (ctypes.c_double * 16)(*self.transform.reshape(-1).tolist())
+        return _native.CameraRec(self.kind, 0, t, self.tan_fov, self.aspect, self.focus_distance, self.sensor_size)
+
+    @classmethod
+    def _from_rec(cls, r):
+        return cls(np.array(list(r.transform), np.float64), r.tan_fov, r.aspect, r.kind, r.focus_distance, r.sensor_size)
+
+    def __eq__(self, other):
+        import struct
+        return isinstance(other, Camera) and struct.pack(_CAMR_FMT, *self._fields()) == struct.pack(_CAMR_FMT, *other._fields())
+
+    __hash__ = None
+
+    def _fields(self):
+        return [self.kind & 0xFFFFFFFF, 0] + self.transform.reshape(-1).tolist() + \
+            [self.tan_fov, self.aspect, self.focus_distance, self.sensor_size]
+
+    def __repr__(self):
+        return (f"Camera(kind={self.kind}, tan_fov={self.tan_fov!r}, aspect={self.aspect!r}, "
+                f"focus_distance={self.focus_distance!r}, sensor_size={self.sensor_size!r}, "
+                f"transform={self.transform.tolist()!r})")
+
+
+def _camera_section(blob):
+    import struct
+    magic, version, nsec, _ = struct.unpack_from("<4I", blob, 0)
+    if magic != 0x5452534A or version != 1:
+        raise JsrtError("not a JSRT v1 scene blob")
+    for i in range(nsec):
+        tag, count, off, nbytes = struct.unpack_from("<IIQQ", blob, 16 + 24 * i)
+        if tag == _CAMR:
+            if count != 1 or nbytes != struct.calcsize(_CAMR_FMT) or off + nbytes > len(blob):
+                raise JsrtError("scene blob's CAMR section is not one 168-byte camera record")
+            return off
+    raise JsrtError("scene blob has no camera record")
+
+
+def blob_camera(blob):
+    """The Camera of a scene blob's CAMR record (host-only)."""
+    import struct
+    f = struct.unpack_from(_CAMR_FMT, blob, _camera_section(blob))
+    return Camera(np.array(f[2:18], np.float64), f[18], f[19], f[0], f[20], f[21])
+
+
+def with_camera(blob, camera):
+    """A copy of `blob` with its CAMR record overwritten by `camera`: the scene a view of Scene.render_views is, by
+    definition, a render of.  Host-only; the blob's own camera round-trips to the identical blob.  Raises JsrtError for a
+    blob without a well-formed CAMR section."""
+    import struct
+    blob = bytes(blob)
+    off = _camera_section(blob)
+    rec = struct.pack(_CAMR_FMT, *camera._fields())
+    return blob[:off] + rec + blob[off + len(rec):]
+
+
 class Scene:
     """A JSRT scene blob (include/jsrt_scene.h) uploaded to one HIP device."""
 
@@ -200,6 +288,57 @@ class Scene:
         out = np.empty((H * W, 6), np.float32)
         check(L.jsrt_camera_rays(self._h, ctypes.byref(p), int(sample), out.ctypes.data), "jsrt_camera_rays")
         return out
+
+    def camera(self):
+        """The Camera the scene's blob was loaded with (include/jsrt_views.h jsrt_scene_camera)."""
+        r = _native.CameraRec()
+        check(_native.views_api().jsrt_scene_camera(self._h, ctypes.byref(r)), "jsrt_scene_camera")
+        return Camera._from_rec(r)
+
+    def render_views(self, cameras, width=0, height=0, spp=0, max_depth=0, kind=-1, seed=1, view_seeds=None, max_paths=0,
+                     want_colors=False, device=False, stats=None, stage_events=0, mode=None, **params):
+        """One frame per Camera of `cameras`, all in one wavefront batch (include/jsrt_views.h): view v is, bit for
+        bit, Scene(with_camera(blob, cameras[v])).render(...) with the same arguments and the seed view_seeds[v]
+        (None: `seed` for every view).  Returns rgba uint8 (V, H, W, 4), or (rgba, colors float32 (V, H, W, 4)) with
+        want_colors.  device=True: torch tensors on the scene's device, rendered on the current torch stream through
+        jsrt_render_views_device, no host copy.  stats: a dict that receives the call's stats.  Further keyword
+        arguments are jsrt_params fields (the library refuses x_offset, x_delt > 1 and a foreign device_mask)."""
+        L = _native.views_api()
+        cameras = list(cameras)
+        nv = len(cameras)
+        recs = (_native.CameraRec * max(nv, 1))(*[c._rec() for c in cameras])
+        seeds = None
+        if view_seeds is not None:
+            seeds = np.ascontiguousarray(view_seeds, np.uint32).reshape(-1)
+            if len(seeds) != nv:
+                raise JsrtError("view_seeds must hold one seed per camera")
+        p = self.params(width, height, spp, max_depth, kind, int(seed) & 0xFFFFFFFF, device=self.device, max_paths=max_paths,
+                        stage_events=stage_events, mode=mode_code(mode), **params)
+        hdr = self.header()
+        W = width if width > 0 else hdr["width"]
+        H = height if height > 0 else hdr["height"]
+        st = Stats() if stats is not None else None
+        st_ref = ctypes.byref(st) if st is not None else None
+        seeds_ptr = seeds.ctypes.data if seeds is not None else None
+        shape = (max(nv, 0), H, W, 4)
+        if not device:
+            rgba = np.zeros(shape, np.uint8)
+            colors = np.full(shape, np.nan, np.float32) if want_colors else None
+            check(L.jsrt_render_views(self._h, ctypes.byref(p), recs, nv, seeds_ptr, rgba.ctypes.data,
+                                      colors.ctypes.data if colors is not None else None, st_ref), "jsrt_render_views")
+        else:
+            import torch
+            dev = torch.device("cuda", self.device)
+            rgba = torch.zeros(shape, dtype=torch.uint8, device=dev)
+            colors = torch.full(shape, float("nan"), dtype=torch.float32, device=dev) if want_colors else None
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream().cuda_stream
+                check(L.jsrt_render_views_device(self._h, ctypes.byref(p), recs, nv, seeds_ptr, rgba.data_ptr(),
+                                                 colors.data_ptr() if colors is not None else None, stream, st_ref),
+                      "jsrt_render_views_device")
+        if st is not None:
+            stats.update(st.as_dict())
+        return (rgba, colors) if want_colors else rgba
 
     def close(self):
         if getattr(self, "_h", None):
