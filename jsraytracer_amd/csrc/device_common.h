@@ -102,7 +102,7 @@ JSRT_HD float or0(float x) { return (x != x || x == 0.0f) ? 0.0f : x; }  // `x |
 
 // --------------------------------------------------------------------------------------------
 // keyed RNG (oracle/refharness/keyed_rng.js)
-__device__ __forceinline__ uint32_t mix32(uint32_t h, uint32_t v) {
+JSRT_HD uint32_t mix32(uint32_t h, uint32_t v) {
     h = (h ^ v) * 0x9E3779B1u;
     h ^= h >> 15;
     h *= 0x85EBCA77u;
@@ -110,7 +110,7 @@ __device__ __forceinline__ uint32_t mix32(uint32_t h, uint32_t v) {
     return h;
 }
 // the draw of hash h = mix(mix(pixkey, node), call)
-__device__ __forceinline__ double uniform_of(uint32_t h) {
+JSRT_HD double uniform_of(uint32_t h) {
     const uint32_t hi = mix32(h, 0xA5A5A5A5u) >> 5;  // 27 bits
     const uint32_t lo = mix32(h, 0x5A5A5A5Au) >> 6;  // 26 bits
     // (hi * 2^26 + lo) * 2^-53 with every step exact in f64 (hi * 2^-27 and lo * 2^-53 are exact, their sum
@@ -119,12 +119,12 @@ __device__ __forceinline__ double uniform_of(uint32_t h) {
     return fma((double)hi, 1.0 / 134217728.0, (double)lo * (1.0 / 9007199254740992.0));
 }
 // pixkey = mix(mix(seed, pixel), sample), hoisted per sample
-__device__ __forceinline__ double keyed_uniform(uint32_t pixkey, uint32_t node, uint32_t call) {
+JSRT_HD double keyed_uniform(uint32_t pixkey, uint32_t node, uint32_t call) {
     return uniform_of(mix32(mix32(pixkey, node), call));
 }
 struct Rng {
     uint32_t key, node, calls;
-    __device__ __forceinline__ double next() { return keyed_uniform(key, node, calls++); }
+    JSRT_HD double next() { return keyed_uniform(key, node, calls++); }
 };
 // the same stream from the frame hash h0 = mix(pixkey, node), computed once per ray-tree node (the shadow
 // hand-off carries it in place of the key and the node address)
@@ -216,7 +216,7 @@ struct SinCos2 {
 // within 2^-50 of V8's, as OCML's acos + sincos were (tests/test_sphere_pick_identity.py checks it against the
 // oracle's fdlibm on 4 M arguments and the poles), so the 2^-44 stability margin still decides exactly.  An
 // acos and a sincos less per pick.
-__device__ __forceinline__ void sin_cos_of_acos(double a, double &sin_phi, double &cos_phi) {
+JSRT_HD void sin_cos_of_acos(double a, double &sin_phi, double &cos_phi) {
     sin_phi = sqrt((1.0 - a) * (1.0 + a));
     cos_phi = a;
 }
@@ -249,7 +249,7 @@ __device__ __forceinline__ F3 sphere_pick(R &rng) {
 // OCML's values, with `unstable` set when a product's f32 rounding is not decided within SPHERE_PICK_EPS;
 // sphere_pick_v8 then gives the reference's point from the same two draws.
 template <class R>
-__device__ __forceinline__ F3 sphere_pick_fast(R &rng, bool &unstable) {
+JSRT_HD F3 sphere_pick_fast(R &rng, bool &unstable) {
     const double theta = 2.0 * JS_PI * rng.next();
     const double a = 2.0 * rng.next() - 1.0;
     double sin_t, cos_t, sin_phi, cos_phi;
@@ -1903,8 +1903,13 @@ __device__ __forceinline__ void light_sample(const DScene &S, const LT &Lt, F3 P
 // PhongPathTracingMaterial.scatter (materials.js:398-412)
 // fix (out): 0, or 1 + the RNG call index of the diffuse pick's first draw when the pick was unstable
 // (sphere_pick_fast): the caller recomputes the direction with sphere_pick_v8 before it is cast
-__device__ __forceinline__ bool path_scatter(double mirror_prob, bool has_r, F3 R, F3 N, const ShadeData &d, Rng &rng,
-                                             F3 &dir, F3 &col, uint32_t &fix, bool force) {
+// NODIR (the children are not cast: World.color's last level): whether the child exists and its colour only.  Neither
+// reads the direction: the mirror and specular branches return has_r and a colour fixed before the pick, and
+// scatterDiffuse (materials.js:414-420) always returns a ray, coloured diffusivity / pi.  The pick's two draws are
+// counted, not drawn (the keyed generator's state is the call count), so the refraction side's draws are the same.
+template <bool NODIR = false>
+JSRT_HD bool path_scatter(double mirror_prob, bool has_r, F3 R, F3 N, const ShadeData &d, Rng &rng, F3 &dir, F3 &col,
+                          uint32_t &fix, bool force) {
     fix = 0;
     if (rng.next() < mirror_prob) {
         dir = R;
@@ -1915,17 +1920,77 @@ __device__ __forceinline__ bool path_scatter(double mirror_prob, bool has_r, F3 
     const double probSum = dp + sp;
     if (probSum == 0) return false;
     if (rng.next() < (dp / probSum)) {  // scatterDiffuse: N.plus(Vec.spherePick().to4()).normalized()
-        const uint32_t call = rng.calls;
-        bool unstable;
-        const F3 sp3 = sphere_pick_fast(rng, unstable);
-        if (unstable || force) fix = call + 1;
-        dir = normalized(add(N, sp3));
+        if constexpr (NODIR) {
+            rng.calls += 2;  // spherePick's theta and phi draws
+            dir = N;
+        } else {
+            const uint32_t call = rng.calls;
+            bool unstable;
+            const F3 sp3 = sphere_pick_fast(rng, unstable);
+            if (unstable || force) fix = call + 1;
+            dir = normalized(add(N, sp3));
+        }
         col = scale(d.diff, 1 / JS_PI);
         return true;
     }
     dir = R;  // scatterSpecular: finite smoothness returns R (materials.js:444-445)
     col = d.spec;
     return has_r;
+}
+
+JSRT_HD F3 pick(bool f, F3 a, F3 b) { return f3(f ? a.x : b.x, f ? a.y : b.y, f ? a.z : b.z); }
+JSRT_HD Child pick(bool f, const Child &a, const Child &b) {
+    return Child{pick(f, a.dir, b.dir), pick(f, a.col, b.col), pick(f, a.w, b.w), f ? a.k : b.k};
+}
+// The children of a Phong / Fresnel / path-tracing node in evaluation order (materials.js:277-288, 315-330): returns
+// their number (0..2), ch0 / ch1 {direction, colour, weight, k}, and fix0 / fix1, path_scatter's fix of each child
+// (bit 31: scattered about -N, the refraction side).  rng: the node's frame after its light-sample draws.
+// NODIR: the directions are not computed (path_scatter<true>) and are unspecified; the count, col, w and k are the
+// full form's bit for bit (tests/test_scatter_last_level.py): a Phong child exists by its weight's squared norm, a
+// Fresnel one by kr and has_refr, a path-tracing one by path_scatter's draws, none of which reads a direction.
+template <bool NODIR = false>
+JSRT_HD int scatter_children(int mkind, double mirror_prob, const ShadeData &sd, F3 d, Rng &rng, bool force_fix,
+                             Child &ch0, Child &ch1, uint32_t &fix0, uint32_t &fix1) {
+    const F3 Nn = sd.N;
+    int n = 0;
+    fix0 = 0u;
+    fix1 = 0u;
+    auto push = [&](const Child &c) {  // unconditional selects keep both slots in registers
+        const bool first = n == 0;
+        ch0 = pick(first, c, ch0);
+        ch1 = pick(first, ch1, c);
+        ++n;
+    };
+    if (mkind == JSRT_MAT_PHONG) {  // materials.js:277-288
+        if (dot3(sd.refl, sd.refl) > 0) push(Child{sd.R, f3(1, 1, 1), sd.refl, 1.0});
+        if (dot3(sd.trans, sd.trans) > 0) push(Child{NODIR ? sd.R : normalized(d), f3(1, 1, 1), sd.trans, 1.0});
+    } else {  // materials.js:315-330
+        if (sd.kr > 0) {
+            F3 dir = sd.R, col = f3(1, 1, 1);
+            bool ok = true;
+            uint32_t fx = 0;
+            if (mkind == JSRT_MAT_PATH) ok = path_scatter<NODIR>(mirror_prob, true, sd.R, Nn, sd, rng, dir, col, fx, force_fix);
+            if (ok) {
+                fix0 = fx;  // the first child
+                push(Child{dir, col, sd.refl, sd.kr});
+            }
+        }
+        if (sd.kr < 1) {
+            F3 dir = sd.refr, col = f3(1, 1, 1);
+            bool ok = sd.has_refr;
+            uint32_t fx = 0;
+            if (mkind == JSRT_MAT_PATH)
+                ok = path_scatter<NODIR>(mirror_prob, sd.has_refr, sd.refr, neg(Nn), sd, rng, dir, col, fx, force_fix);
+            if (ok) {
+                if (fx) {  // child n (0 when the reflection side pushed none)
+                    if (n == 0) fix0 = fx | 0x80000000u;
+                    else fix1 = fx | 0x80000000u;
+                }
+                push(Child{dir, col, sd.trans, 1 - sd.kr});
+            }
+        }
+    }
+    return n;
 }
 
 

@@ -116,7 +116,8 @@ struct DCamera {         // cameras.js:18-53
 // MATF_SPEC_CONST the diffuse / specular chain is a constant (mc_const); MATF_SPEC_ZERO the specular colour
 // is the constant (+0, +0, +0) and the smoothness in [0, 1e5] (render_levels.h: no specular power); MATF_PUV a
 // flattened PositionalUVMaterial chain: (u, v) come from DScene::puv of the hit point, not from the geometry
-enum { MATF_UV = 1, MATF_DIFF_CONST = 2, MATF_SPEC_CONST = 4, MATF_SPEC_ZERO = 8, MATF_PUV = 16 };
+// MATF_AMB_CONST the ambient chain is a constant (mc_const: k_shadow_node's single-writer record, render_levels.h HAND_AMB)
+enum { MATF_UV = 1, MATF_DIFF_CONST = 2, MATF_SPEC_CONST = 4, MATF_SPEC_ZERO = 8, MATF_PUV = 16, MATF_AMB_CONST = 32 };
 
 struct DScene {
     const DPrim *prims;

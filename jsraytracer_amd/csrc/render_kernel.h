@@ -97,6 +97,9 @@ struct WArgs {
     int32_t ns;        // light samples per lit node
     int32_t group;     // lanes per node in k_shadow: a power of two >= ns (<= 64), or 1 (serial)
     int32_t shadow_node; // k_shadow_node (one lane per lit node) where the scene and the batch allow it (run_batch)
+    int32_t node_single; // set by run_batch alone, for a batch whose shadow kernel is k_shadow_node: a lit node's record
+                         // {ambient + light sum, info} is written once, by k_shadow_node, and not by k_shade first
+                         // (render_levels.h HAND_AMB; 0 in the pool's own WArgs)
     int32_t chain;     // schedule
     int32_t hybrid;    // chain schedule with side chains (level counts on the device)
     uint32_t cap;      // chain schedule: slots per level (node [L * cap + slot]); npaths without side chains

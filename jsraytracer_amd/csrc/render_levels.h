@@ -193,10 +193,7 @@ __device__ __forceinline__ void write_result(const WArgs &W, uint32_t i, F3 c) {
 
 // (pixel_of, the patch-ordered owned pixel index -> pixel map of a batch: render_plan.h)
 
-__device__ __forceinline__ F3 pick(bool f, F3 a, F3 b) { return f3(f ? a.x : b.x, f ? a.y : b.y, f ? a.z : b.z); }
-__device__ __forceinline__ Child pick(bool f, const Child &a, const Child &b) {
-    return Child{pick(f, a.dir, b.dir), pick(f, a.col, b.col), pick(f, a.w, b.w), f ? a.k : b.k};
-}
+// (pick, the unconditional selects of F3 / Child: device_common.h)
 
 // Tree schedule: level L of the batch occupies pool slots [base, base + count).  Counts live on
 // the device (k_gen writes level 0, k_shade appends level L + 1), so the host enqueues every level
@@ -240,6 +237,23 @@ constexpr uint32_t HAND_DIFF = 0x40000000u;  // plane 2: diff is not the materia
 constexpr uint32_t HAND_R = 0x20000000u;     // plane 3: the specular term needs R
 constexpr uint32_t HAND_SPEC = 0x10000000u;  // plane 4: spec is not the material's constant
 constexpr uint32_t HAND_MAT = 0x0FFFFF00u;   // mat << 8
+// Single-writer batches (WArgs::node_single: k_shadow_node writes a lit node's record, k_shade does not): the tag's
+// material field is 15 bits (staged tables hold at most 4096 materials) and the bits above it carry what the record
+// needs beside the light sum -- the node's info word (hand_info: a lit node's is INFO_HIT | INFO_LIT, its child count
+// and the two INFO_UNIT bits) and where its ambient comes from: the material's constant (S.mc_const), or, HAND_AMB,
+// the record k_shade wrote at the node's index as before (a textured / checkerboard ambient chain, an SDF basecolor).
+constexpr uint32_t HAND_MAT1 = 0x007FFF00u;  // mat << 8
+constexpr uint32_t HAND_AMB = 0x00800000u;   // the ambient is not the material's constant: node[i] holds it
+constexpr int HAND_INFO_SHIFT = 24;          // 4 bits: child count (2), INFO_UNIT0, INFO_UNIT1
+static_assert((size_t)STAB_MAX_WORDS * 16 / sizeof(int32_t) <= (HAND_MAT1 >> 8) + 1, "a staged scene's materials fit HAND_MAT1");
+static_assert(INFO_NCHILD_SHIFT == 2 && INFO_UNIT0 == 32u && INFO_UNIT1 == 64u, "hand_info's packing");
+__device__ __forceinline__ uint32_t hand_info(uint32_t info) {  // a lit node's info word -> the tag's 4 bits
+    return (((info >> INFO_NCHILD_SHIFT) & 3u) | ((info >> 3) & 0xCu)) << HAND_INFO_SHIFT;
+}
+__device__ __forceinline__ uint32_t hand_info_word(uint32_t tag) {  // ... and back
+    const uint32_t p = tag >> HAND_INFO_SHIFT;
+    return INFO_HIT | INFO_LIT | ((p & 3u) << INFO_NCHILD_SHIFT) | ((p & 0xCu) << 3);
+}
 
 // The material data k_shade hands to k_shadow for one lit node (after getBaseFactors), plus the
 // node's RNG frame (its light-sample draws come first, materials.js:244-257).
@@ -446,7 +460,8 @@ __device__ __forceinline__ void surface_data(const DScene &S, const Hit &h, F3 o
 // PUV (a scene with a PositionalUVMaterial, DScene::has_posuv): a MATF_PUV material's (u, v) are the mapping of the
 // hit point (posuv_map.h) and its geometric UV is dead (need_uv false: no cart_to_sph, no atan2).
 constexpr uint32_t INFO_FIX = 1u << 30;
-template <int PF, bool TEX, bool PUV = false>
+// NODIR (k_shade's last level, whose children are not cast): the children without their directions (scatter_children).
+template <int PF, bool TEX, bool PUV = false, bool NODIR = false>
 __device__ __forceinline__ int shade_node(const DScene &S, bool lit, const Hit &h, F3 o, F3 d, uint32_t addr,
                                           uint32_t key, NodeOut &out, Child &ch0, Child &ch1, uint32_t *fixl,
                                           bool force_fix) {
@@ -546,49 +561,59 @@ __device__ __forceinline__ int shade_node(const DScene &S, bool lit, const Hit &
         uint32_t fl = 0;
         if (!(mf & MATF_DIFF_CONST) || sf.has_bc) fl |= HAND_DIFF;  // diff = basecolor x the diffuse chain
         if (!(mf & MATF_SPEC_CONST)) fl |= HAND_SPEC;
+        if constexpr (PF == PF_ANALYTIC)  // (read by single-writer batches only, store_hand: the flat profile's)
+            if (!(mf & MATF_AMB_CONST) || sf.has_bc) fl |= HAND_AMB;
         if (mkind != JSRT_MAT_PHONG && sd.kr != 1.0) fl |= HAND_KR | HAND_R;
         if (!(mf & MATF_SPEC_ZERO) || !(__builtin_isfinite(sd.R.x) && __builtin_isfinite(sd.R.y) && __builtin_isfinite(sd.R.z)))
             fl |= HAND_R;
         out.h.flags = fl;
         rng.calls = (uint32_t)S.light_draws;
     }
-    int n = 0;
+    // the children (scatter_children, device_common.h); NODIR: without their directions, fix0 = fix1 = 0.
+    // The BVH and SDF profiles keep the scatter written out here as before: through the shared function their
+    // k_shade measured slower (bunny 6.03 -> 6.16 ms, dragon 26.84 -> 27.14 ms, each outside its spread;
+    // profiles/node_single_writer_*_ab_cornell.txt section 5), and nothing else of this kernel differs for them.
     uint32_t fix0 = 0u, fix1 = 0u;
-    auto push = [&](const Child &c) {  // unconditional selects keep both slots in registers
-        const bool first = n == 0;
-        ch0 = pick(first, c, ch0);
-        ch1 = pick(first, ch1, c);
-        ++n;
-    };
-    if (mkind == JSRT_MAT_PHONG) {  // materials.js:277-288
-        if (dot3(sd.refl, sd.refl) > 0) push(Child{sd.R, f3(1, 1, 1), sd.refl, 1.0});
-        if (dot3(sd.trans, sd.trans) > 0) push(Child{normalized(d), f3(1, 1, 1), sd.trans, 1.0});
-    } else {  // materials.js:315-330
-        if (sd.kr > 0) {
-            F3 dir = sd.R, col = f3(1, 1, 1);
-            bool ok = true;
-            uint32_t fx = 0;
-            if (mkind == JSRT_MAT_PATH) ok = path_scatter(M.mirror_prob, true, sd.R, Nn, sd, rng, dir, col, fx, force_fix);
-            if (ok) {
-                fix0 = fx;  // the first child
-                push(Child{dir, col, sd.refl, sd.kr});
-            }
-        }
-        if (sd.kr < 1) {
-            F3 dir = sd.refr, col = f3(1, 1, 1);
-            bool ok = sd.has_refr;
-            uint32_t fx = 0;
-            if (mkind == JSRT_MAT_PATH) ok = path_scatter(M.mirror_prob, sd.has_refr, sd.refr, neg(Nn), sd, rng, dir, col, fx, force_fix);
-            if (ok) {
-                if (fx) {  // child n (0 when the reflection side pushed none)
-                    if (n == 0) fix0 = fx | 0x80000000u;
-                    else fix1 = fx | 0x80000000u;
+    int n = 0;
+    if constexpr (PF == PF_ANALYTIC) {
+        n = scatter_children<NODIR>(mkind, M.mirror_prob, sd, d, rng, force_fix, ch0, ch1, fix0, fix1);
+    } else {
+        auto push = [&](const Child &c) {  // unconditional selects keep both slots in registers
+            const bool first = n == 0;
+            ch0 = pick(first, c, ch0);
+            ch1 = pick(first, ch1, c);
+            ++n;
+        };
+        if (mkind == JSRT_MAT_PHONG) {  // materials.js:277-288
+            if (dot3(sd.refl, sd.refl) > 0) push(Child{sd.R, f3(1, 1, 1), sd.refl, 1.0});
+            if (dot3(sd.trans, sd.trans) > 0) push(Child{normalized(d), f3(1, 1, 1), sd.trans, 1.0});
+        } else {  // materials.js:315-330
+            if (sd.kr > 0) {
+                F3 dir = sd.R, col = f3(1, 1, 1);
+                bool ok = true;
+                uint32_t fx = 0;
+                if (mkind == JSRT_MAT_PATH) ok = path_scatter(M.mirror_prob, true, sd.R, Nn, sd, rng, dir, col, fx, force_fix);
+                if (ok) {
+                    fix0 = fx;  // the first child
+                    push(Child{dir, col, sd.refl, sd.kr});
                 }
-                push(Child{dir, col, sd.trans, 1 - sd.kr});
+            }
+            if (sd.kr < 1) {
+                F3 dir = sd.refr, col = f3(1, 1, 1);
+                bool ok = sd.has_refr;
+                uint32_t fx = 0;
+                if (mkind == JSRT_MAT_PATH) ok = path_scatter(M.mirror_prob, sd.has_refr, sd.refr, neg(Nn), sd, rng, dir, col, fx, force_fix);
+                if (ok) {
+                    if (fx) {  // child n (0 when the reflection side pushed none)
+                        if (n == 0) fix0 = fx | 0x80000000u;
+                        else fix1 = fx | 0x80000000u;
+                    }
+                    push(Child{dir, col, sd.trans, 1 - sd.kr});
+                }
             }
         }
     }
-    if (__builtin_expect((fix0 | fix1) != 0u, 0)) {
+    if (!NODIR && __builtin_expect((fix0 | fix1) != 0u, 0)) {
         const uint32_t t = threadIdx.x;
         fixl[t] = fix0;
         fixl[256 + t] = fix1;
@@ -636,11 +661,16 @@ __device__ __forceinline__ F3 add_child(const WArgs &W, uint32_t i, uint32_t j, 
 //   2 {diff} HAND_DIFF  3 {R, hi(kr)} HAND_R  4 {spec} HAND_SPEC  5 {refr, lo(kr)} HAND_KR
 // A colour without its plane is the material's constant (S.mc_const); the material's kind and smoothness
 // come from its record (S.mat).  cornell's walls need 36 B (80 B until round 4), its floor 68 B.
-__device__ __forceinline__ void store_hand(const WArgs &W, uint32_t h, const Handoff &o) {
+// Single-writer batches (W.node_single): the tag also carries HAND_AMB and the node's info word (hand_info above),
+// and a node without HAND_AMB has no 16-B record from k_shade: its 36 B here are all k_shade writes for it.
+// FLAT: the flat profile's k_shade, the only one whose batches can be single-writer ones (the others never set HAND_AMB).
+template <bool FLAT>
+__device__ __forceinline__ void store_hand(const WArgs &W, uint32_t h, const Handoff &o, uint32_t info) {
     float4 *p = W.hand + h;
     const size_t hs = W.hstride;
-    const uint32_t fl = o.flags;
-    const uint32_t tag = ((uint32_t)o.mat << 8) | (o.mask & 0xFFu) | fl;
+    const uint32_t fl = FLAT ? o.flags & ~HAND_AMB : o.flags;
+    uint32_t tag = ((uint32_t)o.mat << 8) | (o.mask & 0xFFu) | fl;
+    if (FLAT && W.node_single) tag |= (o.flags & HAND_AMB) | hand_info(info);
     p[0] = make_float4(o.pos.x, o.pos.y, o.pos.z, u2f(mix32(o.key, o.addr)));
     p[hs] = make_float4(o.N.x, o.N.y, o.N.z, u2f(tag));
     if (fl & HAND_DIFF) p[2 * hs] = make_float4(o.diff.x, o.diff.y, o.diff.z, 0.0f);
@@ -844,10 +874,15 @@ __device__ __forceinline__ void stab_stage(const DScene &S, DScene &SL, int word
 // PUV (a scene with a PositionalUVMaterial, DScene::has_posuv): shade_node's position-mapped UV, a template parameter
 // for the same reason; such a scene always runs <TEX = true, PUV = true>, so the class costs one more instantiation
 // per schedule, not two.
-template <int PF, bool CHAIN, bool STAGE, bool TEX = false, bool PUV = false>
+// LAST (the level with child_depth == 0, flat scenes: run_batch): the children are black without a cast, so the node
+// keeps their count and factors (the resolve adds 0 * col * w * k) and nothing is computed, appended or stored for
+// their rays: shade_node<NODIR>, no append (every thread would append 0), no k_fix_dirs record.  A template
+// parameter, so the other levels' code and registers are what they were.
+template <int PF, bool CHAIN, bool STAGE, bool TEX = false, bool PUV = false, bool LAST = false>
 __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
                                                     : (PF & PF_SDF) ? JSRT_SHADE_OCC_SDF : JSRT_SHADE_OCC) SHADE_ATTR void k_shade(
-    DScene S, WArgs W, int L, int child_depth) {
+    DScene S, WArgs W, int L, int child_depth_arg) {
+    const int child_depth = LAST ? 0 : child_depth_arg;
     const uint32_t t0 = blockIdx.x * 256, tt = t0 + threadIdx.x;
     const LevelRange R = CHAIN ? chain_level(W, L) : level_range(W, L);
     const uint32_t count = R.count, base = R.base, next_base = CHAIN ? 0u : R.base + R.count;
@@ -901,7 +936,7 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
             rkey = W.key[r];
         }
         const Hit h{rt, prim, rctx};
-        nchild = shade_node<PF, TEX, PUV>(SL, W.ns > 0, h, ro, rd, raddr, rkey, out, ch0, ch1, fixl, W.force_fix != 0);
+        nchild = shade_node<PF, TEX, PUV, LAST>(SL, W.ns > 0, h, ro, rd, raddr, rkey, out, ch0, ch1, fixl, W.force_fix != 0);
         out.h.node = CHAIN ? slot : q;  // (k_shadow: node base + this)
         out.h.mask = (uint32_t)S.grid_cells;  // every root
         if (W.bucket && (out.info & INFO_LIT)) {  // the lit node's hand-off slot, ranked by k_extend
@@ -918,7 +953,8 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
     // casts rays of one or two octants that walk the same BVH subtrees (WArgs::child_sort)
     uint32_t co[2] = {0u, 1u};  // offsets of the children from `at`
     uint32_t at = 0, side_at = 0;
-    if (!CHAIN) {
+    if (LAST) {  // no child is appended: the counters of level L + 1 stay 0
+    } else if (!CHAIN) {
         const int nc = child_depth > 0 ? nchild : 0;
         if (W.child_sort)  // (kernel argument: block-uniform, every thread reaches the barriers)
             at = block_append_keyed(W.lvl + L + 1, nc, nchild > 0 ? octant(ch0.dir) : 0, nchild > 1 ? octant(ch1.dir) : 0,
@@ -936,7 +972,7 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
     }
     // unstable spherePicks: the record for k_fix_dirs, with the slots the children's rays go to below (written
     // before the node's stores, behind which the returning atomic would wait for all of them)
-    if (__builtin_expect(hit && (out.info & INFO_FIX) != 0u, 0) && child_depth > 0) {
+    if (!LAST && __builtin_expect(hit && (out.info & INFO_FIX) != 0u, 0) && child_depth > 0) {
         if (CHAIN) fix_record(W, fixl, out.h.key, out.h.addr, W.hybrid ? nchild : 1, r, side_at);
         else fix_record(W, fixl, out.h.key, out.h.addr, nchild, next_base + at + co[0], next_base + at + co[1]);
     }
@@ -967,12 +1003,17 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADE_OCC_FLAT
     }
     if (nchild > 0 && unit_child(ch0)) out.info |= INFO_UNIT0;
     if (nchild > 1 && unit_child(ch1)) out.info |= INFO_UNIT1;
-    store_node(W, i, out.surf, out.info & ~INFO_FIX);
+    // A lit node of a single-writer batch (W.node_single: run_batch launches k_shadow_node for this level) whose ambient
+    // is its material's constant, and which has a hand-off slot, gets its record from k_shadow_node alone: {ambient +
+    // light sum, info} from the tag.  Every other node's record is written here.
+    const uint32_t info = out.info & ~INFO_FIX;
+    const bool by_shadow = PF == PF_ANALYTIC && W.node_single && (info & INFO_LIT) && !(out.h.flags & HAND_AMB) && hslot != ~0u;
+    if (!by_shadow) store_node(W, i, out.surf, info);
     // (The record at the node's own index -- coalesced 16-B stores -- with k_shadow gathering it through hnode:
     // k_shade -1.5 ms, k_shadow +2.9 ms per cornell frame, profiles/r05_s5_s6_ab.txt; the scatter stays here.)
-    if (out.info & INFO_LIT) {
-        if (!W.bucket) store_hand(W, q, out.h);
-        else if (hslot != ~0u) store_hand(W, hslot, out.h);
+    if (info & INFO_LIT) {
+        if (!W.bucket) store_hand<PF == PF_ANALYTIC>(W, q, out.h, info);
+        else if (hslot != ~0u) store_hand<PF == PF_ANALYTIC>(W, hslot, out.h, info);
     }
     if (nchild > 0) store_child(W, i, 0, ch0);
     if (nchild > 1) store_child(W, i, 1, ch1);
@@ -1042,10 +1083,11 @@ __device__ __forceinline__ F3 mc_const3(const DScene &S, int m) {  // a constant
 }
 // A lit node's hand-off planes (store_hand; h1 = plane 1, already loaded) decoded into the material data of
 // colorFromLightSample: sd, the material's kind, and (returned) whether the specular term goes without R
+// (matmask: HAND_MAT, or HAND_MAT1 in a single-writer batch)
 __device__ __forceinline__ bool hand_decode(const DScene &S, const float4 &h1, const float4 *hp, size_t hs, ShadeData &sd,
-                                            int &mkind) {
+                                            int &mkind, uint32_t matmask = HAND_MAT) {
     const uint32_t tag = f2u(h1.w);
-    const jsrt_rec_material &M = S.mat[(tag & HAND_MAT) >> 8];
+    const jsrt_rec_material &M = S.mat[(tag & matmask) >> 8];
     sd.N = f3(h1.x, h1.y, h1.z);
     sd.diff = (tag & HAND_DIFF) ? f3(hp[2 * hs].x, hp[2 * hs].y, hp[2 * hs].z) : mc_const3(S, M.diffuse);
     sd.spec = (tag & HAND_SPEC) ? f3(hp[4 * hs].x, hp[4 * hs].y, hp[4 * hs].z) : mc_const3(S, M.specular);
@@ -1200,14 +1242,18 @@ __global__ __launch_bounds__(256, PF == PF_ANALYTIC ? JSRT_SHADOW_OCC_FLAT : JSR
     if (lit && s == 0) W.node[i] = make_float4(ret.x, ret.y, ret.z, nd.w);
 }
 
-// k_shadow with one lane per lit node (JSRT_SHADOW_NODE, run_batch's shadow_node_ok): for a flat scene with
+// k_shadow with one lane per lit node (JSRT_SHADOW_NODE, run_batch's node_form): for a flat scene with
 // LDS-staged tables, a bucketed hand-off and ONE area light of 2..NS samples.  What depends only on the node is
 // done once instead of once per sample lane: the hand-off planes and the tag are loaded and decoded once, the
 // material -> colour chain is followed once, each shadow root's record is loaded and the origin's share of its
 // cull and of its local transform computed once for the node's samples (world_any_node), and the samples are
 // added in a register in the reference's order (the SERIAL branch's sum: no shuffles).  Every hand-off slot
 // below the level's lit total is a lit node (DESIGN.md §4.2 "lit = in"), so the node record is not read before
-// the casts: its load is issued early and consumed by the final store.  Results are k_shadow's bit for bit.
+// the casts.  Such a batch is a single-writer batch (WArgs::node_single, set by run_batch with this launch): the
+// record {ambient + light sum, info} is written here alone, from the tag's info bits and the material's constant
+// ambient, and no record is loaded; only a node whose ambient is no constant (HAND_AMB) has a record from k_shade,
+// whose load is issued early (once plane 1, which holds the tag, has arrived) and consumed by the final store.
+// Results are k_shadow's bit for bit.
 #ifndef JSRT_SHADOW_NODE_OCC
 #define JSRT_SHADOW_NODE_OCC 5
 #endif
@@ -1230,7 +1276,12 @@ __global__ __launch_bounds__(256, JSRT_SHADOW_NODE_OCC) void k_shadow_node(DScen
     // slots lie below cap, tree nodes below the level's count)
     const bool lit = in && q < (CHAIN ? W.cap : count);
     const uint32_t i = base + (lit ? q : 0u);
-    const float4 nd = W.node[i];  // the ambient and the info word: consumed by the store at the end
+    // The ambient and the info word, consumed by the store at the end.  Single-writer batch (W.node_single): from the
+    // tag -- the material's constant ambient and hand_info -- and the node's record is neither loaded nor waited
+    // for; only a node whose ambient is no constant (HAND_AMB) has one from k_shade.
+    const bool single = W.node_single != 0;  // (kernel argument: uniform)
+    float4 nd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!single || (lit && (tag & HAND_AMB))) nd = W.node[i];
     DScene SL = S;
     stab_stage(S, SL, S.stab_words_shadow, false);
     if (!lit) return;
@@ -1238,7 +1289,14 @@ __global__ __launch_bounds__(256, JSRT_SHADOW_NODE_OCC) void k_shadow_node(DScen
     const F3 P = f3(h0.x, h0.y, h0.z);
     ShadeData sd;
     int mkind;
-    const bool no_r = hand_decode(SL, h1, hp, hs, sd, mkind);
+    const bool no_r = hand_decode(SL, h1, hp, hs, sd, mkind, single ? HAND_MAT1 : HAND_MAT);
+    if (single) {
+        if (!(tag & HAND_AMB)) {
+            const F3 amb = mc_const3(SL, SL.mat[(tag & HAND_MAT1) >> 8].ambient);
+            nd.x = amb.x, nd.y = amb.y, nd.z = amb.z;
+        }
+        nd.w = u2f(hand_info_word(tag));
+    }
     // per sample: the light sample and its unshadowed colour (sample_unshadowed's per-sample part)
     F3 d[NS], c[NS];
     uint32_t live = 0u;
@@ -1575,8 +1633,16 @@ void material_uv_pf(const DScene &S, const float *rays, uint32_t n, float *uv, i
 // blocks exit at once; a count above the bound sets LVL_UNDER and the frame is redone);
 // levels are reduced bottom-up afterwards.
 template <int PF, bool CHAIN>
-void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t st, KernelTimes *kt,
+void run_batch(const DScene &S, const RenderArgs &A, const WArgs &pool_args, hipStream_t st, KernelTimes *kt,
                const std::vector<size_t> &bound, const BatchSync *sync) {
+    // The batch's shadow kernel is the node-per-lane k_shadow_node: a flat scene with LDS-staged tables and a bucketed
+    // hand-off, one area light without a Sphere geometry, 2..4 samples on lanes of their own (not JSRT_SHADOW_SERIAL),
+    // and the knob (JSRT_SHADOW_NODE) not 0.  Decided once, here: the launch below and WArgs::node_single (k_shade
+    // leaves a lit node's record to k_shadow_node) read the same word, so no batch has one without the other.
+    const bool node_form = PF == PF_ANALYTIC && S.stab_words_shadow > 0 && pool_args.shadow_node && pool_args.bucket &&
+                           S.n_lights == 1 && !S.sphere_lights && pool_args.ns > 1 && pool_args.ns <= 4 && pool_args.group > 1;
+    WArgs W = pool_args;
+    W.node_single = node_form ? 1 : 0;
     auto accum_wait = [&] { if (sync && sync->wait) (void)hipStreamWaitEvent(st, sync->wait, 0); };
     auto accum_done = [&] { if (sync && sync->done) (void)hipEventRecord(sync->done, st); };
     const hipStream_t ss = (sync && sync->aux) ? sync->aux : st;  // k_shadow's stream
@@ -1623,6 +1689,22 @@ void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t
         timed(KT_SHADE, [&] {
             const bool staged = PF == PF_ANALYTIC && S.stab_words > 0;  // the LDS-staged shading tables
             const size_t sl = staged ? (size_t)S.stab_words * 16 : 0;
+            if constexpr (PF == PF_ANALYTIC) {
+                // the last level of a flat scene: k_shade<LAST>, the children without their directions (not measured
+                // on the BVH and SDF profiles, which keep the full form)
+                if (child_depth == 0) {
+                    auto last = [&](auto stage, auto tex, auto puv) {
+                        constexpr bool ST = decltype(stage)::value, TX = decltype(tex)::value, PU = decltype(puv)::value;
+                        hipLaunchKernelGGL((k_shade<PF, CHAIN, ST, TX, PU, true>), dim3(grid_ub(ub)), dim3(256), ST ? sl : 0, st, S, W, L, 0);
+                    };
+                    using T = std::true_type;
+                    using F = std::false_type;
+                    if (S.has_posuv) staged ? last(T{}, T{}, T{}) : last(F{}, T{}, T{});
+                    else if (S.has_textures) staged ? last(T{}, T{}, F{}) : last(F{}, T{}, F{});
+                    else staged ? last(T{}, F{}, F{}) : last(F{}, F{}, F{});
+                    return;
+                }
+            }
             if (S.has_posuv) {  // the PUV instantiations: position-mapped UVs (and the sampler, should a chain need it)
                 if (staged)
                     hipLaunchKernelGGL((k_shade<PF, CHAIN, PF == PF_ANALYTIC, true, true>), dim3(grid_ub(ub)), dim3(256), sl, st, S, W, L, child_depth);
@@ -1676,7 +1758,7 @@ void run_batch(const DScene &S, const RenderArgs &A, const WArgs &W, hipStream_t
                     // one lane per lit node (k_shadow_node): a flat scene with staged tables and a bucketed hand-off,
                     // one area light without a Sphere geometry, 2..4 samples; everything else keeps k_shadow
                     if constexpr (FLAT_PF) {
-                        if (W.shadow_node && W.bucket && S.n_lights == 1 && !S.sphere_lights && W.ns > 1 && W.ns <= 4) {
+                        if (node_form) {
                             hipLaunchKernelGGL((k_shadow_node<PF, CHAIN, 4>), dim3(grid_ub(ub)), dim3(256), sl, ss, S, W, L);
                             return;
                         }

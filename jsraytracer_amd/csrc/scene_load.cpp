@@ -1119,12 +1119,14 @@ struct Loader {
             for (int b = 0; b < 256; ++b) S.tex_q255.push_back((double)b / 255.0);  // `data[i] / 255`, correctly rounded
         }
         mc_constants();
-        // constant diffuse / specular colours (k_shadow reads them from mc_const, not the hand-off)
+        // constant diffuse / specular colours (k_shadow reads them from mc_const, not the hand-off), and a constant
+        // ambient one (k_shadow_node's single-writer record takes it from there: render_levels.h HAND_AMB)
         for (size_t i = 0; i < S.mat.size(); ++i) {
             const jsrt_rec_material &M = S.mat[i];
             if (M.kind == JSRT_MAT_SOLID || M.kind == JSRT_MAT_TRANSPARENT) continue;
             const float *d = &S.mc_const[4 * (size_t)M.diffuse], *sp = &S.mc_const[4 * (size_t)M.specular];
             if (d[3] != 0.0f) S.mat_flags[i] |= MATF_DIFF_CONST;
+            if (S.mc_const[4 * (size_t)M.ambient + 3] != 0.0f) S.mat_flags[i] |= MATF_AMB_CONST;
             if (sp[3] != 0.0f) {
                 S.mat_flags[i] |= MATF_SPEC_CONST;
                 uint32_t b[3];
